@@ -1,6 +1,22 @@
 """Benchmark: GAT layer forward+backward edges/s on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload syn100k|r15|...]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds the graph
+and the layer, runs W warm-up steps, times the K steps (ONE replay of a HIP graph that
+holds exactly those K steps, after one untimed replay; ``--eager``: K eager steps),
+writes the last timed step's outputs with ``--dump-outputs`` and prints one JSON line
+(``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, ...).
+``--full`` adds everything else described below: the eager pass with HIP events around
+every edge-kernel launch (the rooflines), the further legs, the CPU baselines and the
+detail file.
+
+``--dump-outputs DIR`` writes what the last timed step handed back -- the layer output
+``u`` (and ``v`` on the bipartite workloads) and the gradients of W, a_l and a_r -- as
+``DIR/<name>.npy`` in float32, at most 64 MB in all (larger outputs: a fixed seeded
+sample of their rows).  Graph, features, parameters and upstream gradients come from
+fixed seeds, so two builds run with the same arguments see identical inputs.
 
 One step = one full GAT attention layer forward + backward over the whole graph
 (SURVEY.md §8d, config C4 "synthetic CSR graph 100k nodes / 2M edges, 128-dim
@@ -13,13 +29,13 @@ Inputs are resident in HBM before the timed region.  For N > 1 GPUs the layer do
 not shard (SURVEY.md §8e "replicas only"): every rank runs its own replica and value
 = total edges over all ranks / max-over-ranks time ("scaling": "weak").
 
-The K timed steps run twice: eagerly, with HIP events around every edge-kernel launch
-(the rooflines), then as ONE replay of a HIP graph that holds exactly those K steps
+With ``--full`` the K timed steps run twice: eagerly, with HIP events around every
+edge-kernel launch (the rooflines), then as ONE replay of a HIP graph that holds exactly those K steps
 (the headline value: same kernels and work, without the host launch gaps of Python
 autograd; ``--eager`` reports the eager pass instead).  Both are bracketed by a
 barrier + synchronize and maxed over ranks.
 
-Further legs in the same JSON line (same timing rules):
+Further legs in the same JSON line (``--full``; same timing rules):
   * ``bf16``    config C3 at C4 (bf16 tables, bf16 MFMA projection);
   * ``syn2m``   the cache-busting variant (2M nodes, 40M edges: a 1 GB fp32 table
                 outside the 256 MB Infinity Cache), fp32 and bf16;
@@ -324,8 +340,10 @@ class Layer:
     ``v_branch`` also aggregates v = att.T @ h2 (Ablation.py:273)."""
 
     def __init__(self, dev, rowptr, col, n, m, fin, H, F, seed, dtype=torch.float32, graph=None,
-                 dropout=0.0, v_branch=False):
+                 dropout=0.0, v_branch=False, keep_last=False):
         import msha_loader
+
+        self.keep_last, self.last = keep_last, None  # --dump-outputs: step() keeps its outputs
 
         msha_loader.load()
         from msha_gnn_amd import _lib
@@ -389,6 +407,39 @@ class Layer:
             out.backward(self.dU)
         else:
             torch.autograd.backward(list(out), [self.dU, self.dV])
+        if self.keep_last:
+            # detached: a reference to ``out`` itself would keep this step's autograd graph,
+            # and with it the parameters' AccumulateGrad nodes, alive into the next step --
+            # nodes made on another stream break the capture of the steps into a HIP graph.
+            # (Inside a HIP graph these are the buffers every replay's last step fills.)
+            self.last = out.detach() if torch.is_tensor(out) else tuple(o.detach() for o in out)
+
+    def snapshot(self):
+        """Copies of what the last step handed back: the layer output(s) and the parameter
+        gradients (name -> device tensor)."""
+        outs = {"u": self.last} if torch.is_tensor(self.last) else dict(zip("uv", self.last))
+        outs.update(grad_W=self.W.grad, grad_al=self.al.grad, grad_ar=self.ar.grad)
+        return {k: t.detach().clone() for k, t in outs.items() if t is not None}
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(d, outs):
+    """``outs`` (name -> tensor) as d/<name>.npy in float32, DUMP_MAX_BYTES in all: an array
+    over its share of the budget leaves as a fixed sample of its rows (numpy PCG64, seed 0,
+    sorted), the same rows in every run."""
+    os.makedirs(d, exist_ok=True)
+    small = sum(t.numel() * 4 for t in outs.values() if t.numel() * 4 <= (1 << 20))
+    big = [k for k, t in outs.items() if t.numel() * 4 > (1 << 20)]
+    share = (DUMP_MAX_BYTES - small) // max(len(big), 1)
+    for name, t in outs.items():
+        row_bytes = 4 * max(t[0].numel(), 1)
+        if name in big and t.numel() * 4 > share:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], share // row_bytes,
+                                                           replace=False))
+            t = t[torch.as_tensor(rows, device=t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())
 
 
 class Clock:
@@ -413,11 +464,12 @@ class Clock:
             x = float(tt.item())
         return x
 
-    def timed_graph(self, lay, steps):
+    def timed_graph(self, lay, steps, keep=False):
         """Max-over-ranks seconds of ONE replay of a HIP graph holding exactly `steps`
-        steps (captured after the eager pass, which warmed every cache; one untimed
+        steps (captured after the eager steps, which warmed every cache; one untimed
         replay first).  Same kernels, same work as the eager steps without the host
-        launch gaps (~2-10 us per launch, Python autograd).  None if capture fails."""
+        launch gaps (~2-10 us per launch, Python autograd).  None if capture fails.
+        ``keep``: lay.outputs = copies of the timed replay's last step's outputs."""
         ok, g = 1, None
         try:
             g = torch.cuda.CUDAGraph()
@@ -441,15 +493,21 @@ class Clock:
         g.replay()
         self.barrier()
         dt_ = self.max_over_ranks(time.perf_counter() - t0)
+        if keep:  # before the graph and its memory pool go
+            lay.outputs = lay.snapshot()
         del g
         return dt_
+
+    def warm(self, lay, warmup):
+        """`warmup` untimed eager steps (code objects loaded, workspaces allocated)."""
+        for _ in range(warmup):
+            lay.step()
+        self.barrier()
 
     def timed(self, lay, steps, warmup):
         """(max-over-ranks seconds for `steps` eager steps, mean fwd-kernel ms, launches);
         lay.kernel_ms: mean HIP-event ms of every bracketed edge-kernel launch."""
-        for _ in range(warmup):
-            lay.step()
-        self.barrier()
+        self.warm(lay, warmup)
         lay.MF.KERNEL_EVENTS = {}
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -542,16 +600,37 @@ def edge_kernels(lay, n, m, e, H, F, s, workload=None):
 
 
 def layer_leg(clock, dev, label, rowptr, col, n, m, fin, H, F, steps, warmup, world, eager,
-              dtype=torch.float32, graph=None, dropout=0.0, v_branch=False, workload=None):
-    """One timed layer configuration: edges/s (HIP-graph replay unless eager), the forward
-    kernel's roofline and the edge-kernel table.  Returns (dict, layer's graph)."""
+              dtype=torch.float32, graph=None, dropout=0.0, v_branch=False, workload=None,
+              full=True, dump=None):
+    """One timed layer configuration: edges/s (HIP-graph replay unless eager) and, with
+    ``full``, the forward kernel's roofline and the edge-kernel table from an eager pass of
+    the same steps under HIP events.  ``dump``: directory for the last timed step's outputs
+    (rank 0).  Returns (dict, layer's graph)."""
     e = len(col)
     s = 2 if dtype == torch.bfloat16 else 4
+    keep = dump is not None
     lay = Layer(dev, rowptr, col, n, m, fin, H, F, seed=1, dtype=dtype, graph=graph,
-                dropout=dropout, v_branch=v_branch)
-    dte, k_ms, nl = clock.timed(lay, steps, warmup)
-    dtg = None if eager else clock.timed_graph(lay, steps)
+                dropout=dropout, v_branch=v_branch, keep_last=keep)
+    dte = None
+    if full or eager:
+        dte, k_ms, nl = clock.timed(lay, steps, warmup)
+    else:  # (at least one eager step before the capture: code objects, workspaces)
+        clock.warm(lay, max(warmup, 1))
+    dtg = None if eager else clock.timed_graph(lay, steps, keep)
+    if dtg is None and dte is None:  # capture failed in a plain run: time the eager steps
+        dte, k_ms, nl = clock.timed(lay, steps, 0)
     dt = dtg if dtg is not None else dte
+    if keep:
+        if dtg is None:  # the eager steps were the timed ones
+            lay.outputs = lay.snapshot()
+        if int(os.environ.get("RANK", "0")) == 0:
+            dump_outputs(dump, lay.outputs)
+    if not full:
+        res = {"workload": label, "value": world * e * steps / dt, "unit": "edges/s",
+               "ms_per_step": dt / steps * 1e3, "dtype": "bf16" if s == 2 else "f32"}
+        g = lay.graph
+        del lay
+        return res, g
     if lay.bip:
         fb = bip_fwd_bytes(n, m, e, H, F, s, hs=lay.v_branch)
         bpat = bip_kernel_patterns(H, F, s == 2, lay.v_branch)[0]
@@ -1349,9 +1428,10 @@ _KSHORT = {"msha_edge_attention_fwd": "fwd", "msha_edge_attention_bwd_fused": "b
 
 
 def compact_line(out: dict, detail_path: str) -> dict:
-    """The stdout line: the contract keys, the headline roofline and CPU baseline, and a
-    compact ``legs`` map (per leg value / ms_per_step / frac / traffic) plus each leg's
-    edge-kernel HBM fractions; everything else stays in ``detail_path``."""
+    """The stdout line: the contract keys and, for a ``--full`` run, the headline roofline
+    and CPU baseline, and a compact ``legs`` map (per leg value / ms_per_step / frac /
+    traffic) plus each leg's edge-kernel HBM fractions; everything else stays in
+    ``detail_path``."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
             "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")
     line = {k: out[k] for k in keep if k in out}
@@ -1361,6 +1441,8 @@ def compact_line(out: dict, detail_path: str) -> dict:
                      "ranks": [{k: r.get(k) for k in ("rank", "local_rank", "device",
                                                       "pci_bus_id") if k in r}
                                for r in rk.get("ranks", [])]}
+    if "roofline" not in out:  # a plain run: the headline alone
+        return line
     ro = out.get("roofline") or {}
     line["roofline"] = {k: (_sig(ro.get(k)) if isinstance(ro.get(k), float) else ro.get(k))
                         for k in ("kernel", "bound", "achieved", "peak", "unit", "frac",
@@ -1453,6 +1535,13 @@ def main():
     ap.add_argument("--eager", action="store_true",
                     help="report the eager launches (no HIP-graph replay of the timed steps)")
     ap.add_argument("--no-dropout-leg", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the rooflines (an eager pass under HIP events), the further legs "
+                         "(dropout, bf16, syn2m, bip1m, link scoring, train steps), the CPU "
+                         "baselines and the detail file; the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (u, v, the gradients of W, a_l, "
+                         "a_r) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--detail", default=os.path.join("gpurun_out", "bench_detail.json"),
                     help="where the full per-leg detail goes (stdout carries the compact line)")
     ap.add_argument("--dry-run", action="store_true",
@@ -1508,7 +1597,23 @@ def main():
     K, Wu = args.steps, args.warmup
     # (bip1m: the OursLayer3 core with its u and v aggregates, as the default run's leg)
     head, graph = layer_leg(clock, dev, f"gat_layer_{wl}", rowptr, col, n, m, fin, H, F, K, Wu,
-                            world, args.eager, workload=wl, v_branch=wl == "bip1m")
+                            world, args.eager, workload=wl, v_branch=wl == "bip1m",
+                            full=args.full, dump=args.dump_outputs)
+    if not args.full:  # a plain run: the headline alone
+        if rank == 0:
+            out = {"metric": METRIC, "value": head["value"], "unit": "edges/s", "n_gpus": world,
+                   "steps": K, "warmup": Wu, "ms_per_step": head["ms_per_step"],
+                   "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                   "dtype": "f32", "data": "synthetic",
+                   "config": {"workload": f"gat_layer_{wl}", "nodes": n, "cols": m, "edges": e,
+                              "in_features": fin, "heads": H, "feat": F,
+                              "parallelism": f"replicas{world}"},
+                   "ranks": census}
+            sys.stdout.flush()
+            os.write(json_fd, (dumps_line(compact_line(out, None)) + "\n").encode())
+        if dist:
+            tdist.destroy_process_group()
+        return
     drop_leg = None
     if not args.no_dropout_leg:
         # the reference's training forward drops attention at p = 0.5 (Ablation.py:271):

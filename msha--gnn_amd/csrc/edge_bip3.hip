@@ -285,7 +285,14 @@ __device__ __forceinline__ void st_frag(T* st, const f32x16& acc, int n, int t, 
 #pragma unroll
   for (int i = 0; i < 16; ++i) st[((i & 3) + 8 * (i >> 2) + 4 * c) * Stg<T>::P + 32 * n + t] = (T)acc[i];
 }
-template <typename T>
+// VOFF: the tile's byte offset rides in the vector offset and the scalar offset stays 0.  A
+// 16-byte store reads its data registers after issue, and the compiler keeps the one wait
+// state before a VALU write of them only for stores without a scalar-offset register: with
+// r0 * RB as the scalar offset, the fp32 COEF backward computed the next piece's address into
+// the previous store's first data register (16 elements of one d_hs tile held byte offsets on
+// the kernel's first launch).  The backward stores with VOFF; the forward's stores have no
+// such write behind them and keep the scalar offset.
+template <typename T, bool VOFF = false>
 __device__ __forceinline__ void flush_rows(const T* st, rsrc_t rs, int32_t r0, int h, int lane) {
   constexpr int CPR = kF * (int)sizeof(T) / 16;  // 16-byte pieces per row
   constexpr int NP = 32 * CPR / 64;              // pieces per lane
@@ -293,9 +300,12 @@ __device__ __forceinline__ void flush_rows(const T* st, rsrc_t rs, int32_t r0, i
   for (int k = 0; k < NP; ++k) {
     const int q = lane + 64 * k, row = q / CPR, pc = q % CPR;
     const u32x4_t v = *reinterpret_cast<const u32x4_t*>(st + row * Stg<T>::P + pc * (16 / (int)sizeof(T)));
-    __builtin_amdgcn_raw_buffer_store_b128(
-        v, rs, (uint32_t)row * Tab<T>::RB + (uint32_t)(h * kF) * sizeof(T) + (uint32_t)pc * 16u,
-        (uint32_t)r0 * Tab<T>::RB, 0);
+    const uint32_t in_row = (uint32_t)(h * kF) * sizeof(T) + (uint32_t)pc * 16u;
+    if constexpr (VOFF)
+      __builtin_amdgcn_raw_buffer_store_b128(v, rs, (uint32_t)(r0 + row) * Tab<T>::RB + in_row, 0u, 0);
+    else
+      __builtin_amdgcn_raw_buffer_store_b128(v, rs, (uint32_t)row * Tab<T>::RB + in_row,
+                                             (uint32_t)r0 * Tab<T>::RB, 0);
   }
 }
 
@@ -1058,7 +1068,7 @@ __global__ void __launch_bounds__(kWaves * 64) bip3_bwd_kernel(
           }
           st_frag<T>(stg, acc, n, t, c);
         }
-        flush_rows<T>(stg, r_dhs, r0, h, lane);
+        flush_rows<T, true>(stg, r_dhs, r0, h, lane);
         if (BIP3_HSLATE && KR == KS) {
 #pragma unroll
           for (int ks = 4; ks < KS; ++ks) load_piece(ks, r0 + kTile, ring[ks < KR ? ks : 0]);

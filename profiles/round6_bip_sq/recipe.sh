@@ -7,7 +7,7 @@ OUT="$R/gpurun_out/pmc_$1"
 WL="$2"; RX="$3"; shift 3
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-dropout-leg --no-r15 $*"
+B="$R/bench.py --full --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-dropout-leg --no-r15 $*"
 timeout -s KILL 120 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o run -- python3 $B > "$OUT/trace.log" 2>&1 || { echo "trace failed"; tail -3 "$OUT/trace.log"; exit 3; }
 i=0
 for C in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_WAVES SQ_VALU_MFMA_BUSY_CYCLES" "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_BRANCH" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" "FETCH_SIZE" "WRITE_SIZE"; do

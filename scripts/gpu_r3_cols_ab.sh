@@ -9,6 +9,6 @@ for V in "" colspf; do
     tests/test_gpu_parity_full.py tests/test_gpu_row_scores.py tests/test_gpu_fullsize.py > "$OUT/tests_$V.log" 2>&1
   rc=$?; echo "[$V] $(tail -1 "$OUT/tests_$V.log")"
   [ $rc -ne 0 ] && { grep -E "FAILED|Error" "$OUT/tests_$V.log" | head; exit $rc; }
-  MSHA_GNN_LIB="$L" timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-link-score --no-r15 --no-bip1m > "$OUT/bench_$V.json" 2> "$OUT/bench_$V.err" || { echo "bench $V failed"; tail "$OUT/bench_$V.err"; exit 2; }
+  MSHA_GNN_LIB="$L" timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-link-score --no-r15 --no-bip1m > "$OUT/bench_$V.json" 2> "$OUT/bench_$V.err" || { echo "bench $V failed"; tail "$OUT/bench_$V.err"; exit 2; }
   echo "[$V]"; python3 scripts/bench_brief.py "$OUT/bench_$V.json" 2>/dev/null | head -20
 done

@@ -6,7 +6,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
   -k "edge or fused or rowterms or parity_full or modules or ours" > gpurun_out/ab_tests.log 2>&1
 rc=$?; tail -3 gpurun_out/ab_tests.log; [ $rc -eq 0 ] || exit $rc
 for W in syn2m syn100k; do
-  B="bench.py --workload $W --steps 10 --warmup 3 --no-cpu-baseline --no-link-score --no-r15 --no-dropout-leg"
+  B="bench.py --full --workload $W --steps 10 --warmup 3 --no-cpu-baseline --no-link-score --no-r15 --no-dropout-leg"
   for A in default ${ALTS:-}; do
     O=gpurun_out/ab_${W}_${A}
     if [ "$A" = default ]; then

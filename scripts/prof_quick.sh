@@ -6,7 +6,7 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$R/gpurun_out/pq_$TAG"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 export $ENVS
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o run -- python3 "$R/bench.py" $BARGS > "$OUT/bench.log" 2>&1 || { echo "trace failed"; tail -20 "$OUT/bench.log"; exit 3; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o run -- python3 "$R/bench.py" --full $BARGS > "$OUT/bench.log" 2>&1 || { echo "trace failed"; tail -20 "$OUT/bench.log"; exit 3; }
 python3 - "$OUT" <<'PY'
 import csv, sys
 out = sys.argv[1]

@@ -7,7 +7,7 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$R/gpurun_out/prof_$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --steps 20 --warmup 5 --no-cpu-baseline $*"
+B="$R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $*"
 (cd "$R" && python3 -c "import bench; print(bench.kernel_source_id())") > "$OUT/source_id.txt"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o run -- python3 $B > "$OUT/bench_trace.log" 2>&1 || { echo "trace pass failed"; tail -20 "$OUT/bench_trace.log"; exit 2; }
 for C in FETCH_SIZE WRITE_SIZE; do

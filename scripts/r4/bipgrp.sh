@@ -11,7 +11,7 @@ MSHA_GNN_LIB=$V $T 400 python -u -m pytest -x -q --timeout 200 --timeout-method 
 tail -1 gpurun_out/r4/bipg16_tests.log
 for L in "" $V; do
   tag=$([ -z "$L" ] && echo g8 || echo g16)
-  MSHA_GNN_LIB=${L:-msha--gnn_amd/lib/libmsha_gnn.so} $T 300 python -u bench.py --workload bip1m --steps 10 --warmup 3 \
+  MSHA_GNN_LIB=${L:-msha--gnn_amd/lib/libmsha_gnn.so} $T 300 python -u bench.py --full --workload bip1m --steps 10 --warmup 3 \
     --no-cpu-baseline --no-dropout-leg > gpurun_out/r4/bip1m_$tag.json 2> gpurun_out/r4/bip1m_$tag.err \
     || { tail -20 gpurun_out/r4/bip1m_$tag.err; exit 1; }
   echo "== $tag"; python scripts/bench_brief.py gpurun_out/r4/bip1m_$tag.json | head -12

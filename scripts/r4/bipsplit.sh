@@ -13,7 +13,7 @@ MSHA_BIP_SPLIT=1 $T 300 python -u -m pytest -x -q --timeout 200 --timeout-method
   > gpurun_out/r4/bipsplit_off.log 2>&1 || { tail -40 gpurun_out/r4/bipsplit_off.log; exit 1; }
 tail -2 gpurun_out/r4/bipsplit_off.log
 for SP in 1 0; do
-MSHA_BIP_SPLIT=$SP $T 300 python -u bench.py --workload bip1m --steps 10 --warmup 3 --no-cpu-baseline \
+MSHA_BIP_SPLIT=$SP $T 300 python -u bench.py --full --workload bip1m --steps 10 --warmup 3 --no-cpu-baseline \
   --no-r15 --no-dropout-leg > gpurun_out/r4/bip1m_s$SP.json 2> gpurun_out/r4/bip1m_s$SP.err || { tail -20 gpurun_out/r4/bip1m_s$SP.err; exit 1; }
 python scripts/bench_brief.py gpurun_out/r4/bip1m_s$SP.json | head -6
 done

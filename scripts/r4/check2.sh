@@ -15,7 +15,7 @@ $T 600 python -u -m pytest -x -q -s --timeout 500 --timeout-method thread \
   "tests/test_gpu_parity_full.py::test_ablation3_bf16_model_vs_fp64" > gpurun_out/r4/tests_b.log 2>&1 \
   || { tail -60 gpurun_out/r4/tests_b.log; exit 1; }
 grep -E "bip1m|of elements|passed|failed" gpurun_out/r4/tests_b.log
-$T 300 python -u bench.py --workload bip1m --steps 10 --warmup 3 --no-cpu-baseline \
+$T 300 python -u bench.py --full --workload bip1m --steps 10 --warmup 3 --no-cpu-baseline \
   --no-r15 --no-dropout-leg > gpurun_out/r4/bip1m.json 2> gpurun_out/r4/bip1m.err || { tail -20 gpurun_out/r4/bip1m.err; exit 1; }
 python scripts/bench_brief.py gpurun_out/r4/bip1m.json
 $T 300 python scripts/r4/trainpy_time.py > gpurun_out/r4/trainpy.json 2> gpurun_out/r4/trainpy.err || { tail -20 gpurun_out/r4/trainpy.err; exit 1; }

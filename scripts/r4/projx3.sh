@@ -11,6 +11,6 @@ tail -1 gpurun_out/r4/projx3_tests.log
 GEMM_AB_BIP1M=1 $T 300 python -u scripts/gemm_ab.py > gpurun_out/r4/projx3_ab.log 2>&1 &&
 GEMM_AB_BIP1M=1 MSHA_GNN_LIB=$PWD/msha--gnn_amd/lib/alt/projx0.so $T 300 python -u scripts/gemm_ab.py >> gpurun_out/r4/projx3_ab.log 2>&1 || { tail -20 gpurun_out/r4/projx3_ab.log; exit 1; }
 grep '^{' gpurun_out/r4/projx3_ab.log | grep float32
-$T 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-link-score --no-r15 --no-syn2m --no-bip1m --no-dropout-leg \
+$T 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-link-score --no-r15 --no-syn2m --no-bip1m --no-dropout-leg \
   > gpurun_out/r4/c4.json 2> gpurun_out/r4/c4.err || { tail -20 gpurun_out/r4/c4.err; exit 1; }
 python scripts/bench_brief.py gpurun_out/r4/c4.json

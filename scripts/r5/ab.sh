@@ -8,7 +8,7 @@ export PYTHONUNBUFFERED=1
 i=0
 for v in $VALS; do
   i=$((i+1))  # (file names by index: values may hold paths)
-  env $KNOB=$v timeout -k 10 400 python -u bench.py --workload $WL --no-cpu-baseline $ARGS \
+  env $KNOB=$v timeout -k 10 400 python -u bench.py --full --workload $WL --no-cpu-baseline $ARGS \
     --detail $O/d_$i.json > $O/l_$i.line 2> $O/e_$i.err || { tail -20 $O/e_$i.err; exit 1; }
   echo "== $KNOB=$v"
   python scripts/bench_brief.py $O/d_$i.json | grep -E "${GREP:-.}"

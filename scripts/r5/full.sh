@@ -14,7 +14,7 @@ fi
 $T 120 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 \
   || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-$T 600 python -u bench.py --detail $O/bench_detail.json ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err \
+$T 600 python -u bench.py --full --detail $O/bench_detail.json ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err \
   || { tail -20 $O/bench.err; exit 1; }
 wc -c $O/bench.json
 python scripts/bench_brief.py $O/bench_detail.json

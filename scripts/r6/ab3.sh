@@ -7,7 +7,7 @@ mkdir -p $O
 export PYTHONUNBUFFERED=1
 run() {  # name lib [env]
   local name=$1 lib=$2; shift 2
-  env "$@" MSHA_GNN_LIB=$lib timeout -k 10 300 python -u bench.py --workload bip1m --steps 10 --warmup 3 \
+  env "$@" MSHA_GNN_LIB=$lib timeout -k 10 300 python -u bench.py --full --workload bip1m --steps 10 --warmup 3 \
     --no-cpu-baseline --no-r15 --no-dropout-leg --detail $O/$name.json > $O/$name.line 2> $O/$name.err \
     || { tail -20 $O/$name.err; exit 1; }
   echo "== $name"

@@ -13,7 +13,7 @@ MSHA_GNN_LIB=$A MSHA_BIP3_BWD32=1 timeout -k 10 600 python -u -m pytest -q --tim
 tail -1 $O/tests.log
 run() {  # name lib [env]
   local name=$1 lib=$2; shift 2
-  env "$@" MSHA_GNN_LIB=$lib timeout -k 10 300 python -u bench.py --workload bip1m --steps 10 --warmup 3 \
+  env "$@" MSHA_GNN_LIB=$lib timeout -k 10 300 python -u bench.py --full --workload bip1m --steps 10 --warmup 3 \
     --no-cpu-baseline --no-r15 --no-dropout-leg --detail $O/$name.json > $O/$name.line 2> $O/$name.err \
     || { tail -20 $O/$name.err; exit 1; }
   echo "== $name"

@@ -6,7 +6,7 @@ O=gpurun_out/r6_ab5${TAG}
 mkdir -p $O
 export PYTHONUNBUFFERED=1
 run() {  # name lib
-  MSHA_GNN_LIB=$2 timeout -k 10 300 python -u bench.py --workload bip1m --steps 10 --warmup 3 \
+  MSHA_GNN_LIB=$2 timeout -k 10 300 python -u bench.py --full --workload bip1m --steps 10 --warmup 3 \
     --no-cpu-baseline --no-r15 --no-dropout-leg --detail $O/$1.json > $O/$1.line 2> $O/$1.err \
     || { tail -20 $O/$1.err; exit 1; }
   echo "== $1"

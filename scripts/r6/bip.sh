@@ -13,7 +13,7 @@ if [ -z "$NOTESTS" ]; then
   tail -2 $O/tests.log
 fi
 for v in ${VALS:-1 0}; do
-  MSHA_BIP3=$v $T 300 python -u bench.py --workload bip1m --steps 10 --warmup 3 --no-cpu-baseline \
+  MSHA_BIP3=$v $T 300 python -u bench.py --full --workload bip1m --steps 10 --warmup 3 --no-cpu-baseline \
     --no-r15 --no-dropout-leg --detail $O/bip1m_$v.json > $O/bip1m_$v.line 2> $O/bip1m_$v.err \
     || { tail -20 $O/bip1m_$v.err; exit 1; }
   echo "== MSHA_BIP3=$v"

@@ -13,7 +13,7 @@ fi
 for name in main $ALTS; do
   lib=msha--gnn_amd/lib/libmsha_gnn.so
   [ "$name" != main ] && lib=msha--gnn_amd/lib/alt/$name.so
-  MSHA_GNN_LIB=$lib timeout -k 10 300 python -u bench.py --workload ${WL:-bip1m} --steps 10 --warmup 3 --no-cpu-baseline \
+  MSHA_GNN_LIB=$lib timeout -k 10 300 python -u bench.py --full --workload ${WL:-bip1m} --steps 10 --warmup 3 --no-cpu-baseline \
     --no-r15 --no-dropout-leg --detail $O/$name.json > $O/$name.line 2> $O/$name.err \
     || { tail -20 $O/$name.err; exit 1; }
   echo "== $name"

@@ -6,7 +6,7 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$R/gpurun_out/trace_$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT" -o run -- python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-link-score --no-r15 "$@" > "$OUT/bench.log" 2>&1 || { echo "trace failed"; tail -5 "$OUT/bench.log"; exit 3; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT" -o run -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-link-score --no-r15 "$@" > "$OUT/bench.log" 2>&1 || { echo "trace failed"; tail -5 "$OUT/bench.log"; exit 3; }
 python3 - "$OUT" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/run_kernel_stats.csv", recursive=True)[0]

@@ -207,6 +207,45 @@ def test_bench_line_is_small_strict_json():
     assert {"value", "unit", "cores", "kind", "sample"} <= set(line["cpu_baseline"])
 
 
+def test_plain_line_carries_the_headline_only():
+    """A run without --full prints the contract keys and nothing of the --full legs."""
+    import json
+
+    out = {k: v for k, v in _maximal_out().items()
+           if k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                    "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+                    "ranks")}
+    line = json.loads(bench.dumps_line(bench.compact_line(out, None)))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps",
+              "warmup", "n_gpus", "ranks"):
+        assert k in line, k
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"roofline", "legs", "kernel_frac", "cpu_baseline", "detail"} & set(line)
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs: float32 .npy files, 64 MB in all; an output over the budget leaves
+    as the same sorted row sample in every run, small arrays whole."""
+    import torch
+
+    big = torch.arange(300_000, dtype=torch.float32)[:, None] * torch.ones(1, 64)  # 76.8 MB
+    small = torch.arange(12, dtype=torch.bfloat16).view(3, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"u": big, "grad_W": small})
+    ua, ub = np.load(tmp_path / "a" / "u.npy"), np.load(tmp_path / "b" / "u.npy")
+    ga = np.load(tmp_path / "a" / "grad_W.npy")
+    assert ua.dtype == np.float32 and ga.dtype == np.float32
+    assert ua.nbytes + ga.nbytes <= bench.DUMP_MAX_BYTES < big.numel() * 4
+    assert np.array_equal(ua, ub)
+    rows = ua[:, 0].astype(np.int64)
+    assert len(rows) > 200_000 and np.all(np.diff(rows) > 0)  # a sorted sample of rows
+    assert np.array_equal(ua, big.numpy()[rows])
+    assert np.array_equal(ga, small.float().numpy())
+    whole = torch.ones(1000, 8)
+    bench.dump_outputs(str(tmp_path / "c"), {"u": whole})
+    assert np.array_equal(np.load(tmp_path / "c" / "u.npy"), whole.numpy())
+
+
 def test_bip_kernel_patterns_match_rocprof_names():
     """The bipartite rooflines' PMC lookup names every kernel family (the MFMA kernels of
     edge_bip3.hip, the mask kernels of edge_bip2.hip and the CSR walk of edge_bip.hip) as
