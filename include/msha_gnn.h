@@ -798,6 +798,47 @@ MSHA_API int msha_project_small_bwd(int64_t M, int64_t K, int32_t heads, int32_t
                                     const float* d_el, const float* d_er, float* dX, float* dW,
                                     float* dal, float* dar, msha_stream_t stream);
 
+/* ---- Device-side evaluation (train.py:239-282, model.py:66-92) (ABI 16, added) -------- */
+/* One launch per test batch (ABI 16, added).  For b in [0, B), i = src[b] (src NULL: b)
+ * and y = labels[b], at position r = row_offset + b of the caller's per-row buffers:
+ *   store[r, :] = table[i, :] widened exactly to fp32   (store: (capacity, C), pitch C)
+ *   labels_out[r] = y;  nll[r] = -table[i, y];  pred[r] = lowest index of the row maximum
+ *   conf[y * C + pred[r]] += 1                           (int64 C x C, integer atomic)
+ *   counters[0] += non-finite values in the row;  counters[1] += 1 for a bad row
+ * table: (N, C) of dtype (MSHA_DTYPE_*), row pitch ld elements, 1 <= C <= 1024.  A src in
+ * [-N, 0) wraps as torch's output[source_index]; any other src outside [0, N) or a label
+ * outside [0, C) makes the row bad: nothing is read through either index, the row stores
+ * zeros, nll 0, pred -1, labels_out -1 and touches counters[1] only.  conf and counters
+ * are the caller's, zeroed before the first batch. */
+MSHA_API int msha_eval_rows(int64_t N, int32_t C, int64_t B, int32_t dtype, const void* table,
+                            int64_t ld, const int64_t* src, const int64_t* labels,
+                            int64_t row_offset, float* store, int64_t* labels_out, float* nll,
+                            int64_t* pred, int64_t* conf, int64_t* counters,
+                            msha_stream_t stream);
+/* (ABI 16, added) loss[0] = mean over the chunks [c * chunk, min(n, (c+1) * chunk)) of the
+ * chunk's mean of nll (fp32) -- chunk = n: the mean over all rows; chunk = the batch size:
+ * what train.py:253-254,274 prints.  Every sum runs in a fixed order; no float atomics. */
+MSHA_API int msha_eval_loss(int64_t n, int64_t chunk, const float* nll, float* loss,
+                            msha_stream_t stream);
+/* Tie-aware rank statistic of each of C columns of an (n, >= C) fp32 score store, row
+ * pitch ld (ABI 16, added).  Row b is positive in column k iff labels[b] == cls[k] (cls
+ * NULL: cls[k] = k); binary != 0 (C = 1, cls NULL): iff labels[b] != 0.  Scores compare as
+ * the order-preserving uint32 image of their bits with -0.0 folded onto +0.0 (denormals
+ * stay distinct).  out[4 k + {0, 1, 2, 3}] = P, Nn, U2 = sum over groups of equal score of
+ * pos_g (2 neg_below_g + neg_g), and the column's count of non-finite scores;
+ * AUC_k = U2 / (2 P Nn) in the caller's fp64.  All device arithmetic is integer: the
+ * result does not depend on execution order.  Columns of at most
+ * msha_rank_auc_block_keys() rows are sorted in LDS by one block each and need no
+ * workspace; longer ones take a stable 8-bit LSD radix sort through ws
+ * (msha_rank_auc_workspace_size bytes, 16-byte aligned, contents irrelevant).
+ * 1 <= n < 2^31, 1 <= C <= 65535. */
+MSHA_API size_t msha_rank_auc_workspace_size(int64_t n, int32_t C);
+MSHA_API int msha_rank_auc(int64_t n, int32_t C, const float* scores, int64_t ld,
+                           const int64_t* labels, const int32_t* cls, int32_t binary,
+                           int64_t* out, void* ws, size_t ws_bytes, msha_stream_t stream);
+/* host-only: the largest n the one-block LDS path takes (ABI 16, added) */
+MSHA_API int64_t msha_rank_auc_block_keys(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,12 @@ SIGNATURES = {
     "msha_nll_rows_bwd_flags": (C.c_int, [I64, I64, I64, P, P, P, I32, P, I64, P, P, P]),
     "msha_head_bwd_flagged": (C.c_int, [GP, HPP, I32, P, P, P, F32, U64, F32, U64, P, P, P, P, P,
                                         P, P, P, I64, P, SZ, P]),
+    # device-side evaluation (ABI 16, added)
+    "msha_eval_rows": (C.c_int, [I64, I32, I64, I32, P, I64, P, P, I64, P, P, P, P, P, P, P]),
+    "msha_eval_loss": (C.c_int, [I64, I64, P, P, P]),
+    "msha_rank_auc_workspace_size": (SZ, [I64, I32]),
+    "msha_rank_auc": (C.c_int, [I64, I32, P, I64, P, P, I32, P, P, SZ, P]),
+    "msha_rank_auc_block_keys": (I64, []),
 }
 
 _lib = None

@@ -10,5 +10,5 @@ import torch.nn.functional as F  # noqa: F401
 import _boot  # noqa: F401
 from msha_gnn_amd.graph import normalize_adjacency_matrix  # noqa: F401
 from msha_gnn_amd.layers import GCN, GraphConvolution  # noqa: F401
-from msha_gnn_amd.metrics import (calculate_accuracy, calculate_auc,  # noqa: F401
-                                  calculate_precision_recall)
+from msha_gnn_amd.metrics import (Evaluator, binary_auc, calculate_accuracy,  # noqa: F401
+                                  calculate_auc, calculate_precision_recall)

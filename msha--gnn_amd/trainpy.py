@@ -8,7 +8,9 @@ writes them, with the drop-in directory first on ``sys.path``, into a fresh name
 statement: ``.to(device)`` of the batch, ``optimizer.zero_grad()``, the model forward,
 ``F.nll_loss(output[source_index], recipient_index)``, ``loss.item()``, ``backward()``,
 ``optimizer.step()`` -- torch's Adam, no HIP graph, no fused loss.  Used by
-tests/test_dropin.py and by bench.py's ``train_py_literal`` leg.
+tests/test_dropin.py and by bench.py's ``train_py_literal`` leg.  ``test_epoch`` is
+train.py's ``test()`` (train.py:239-282) over the test split, as written or with the
+device-side metrics (``metrics.Evaluator``).
 
 ``write_year`` writes a year's data in the reference's ``anonymous_data`` formats
 (Adjacent / GDP json, Flow csv with one row per flow, dataset.py:208-237).
@@ -87,9 +89,12 @@ class TrainPy:
         Dataset = ns["dataset"].HigherDataset()
         train_size = int(0.9 * len(Dataset))
         test_size = len(Dataset) - train_size
-        train_dataset, _ = ns["random_split"](Dataset, [train_size, test_size])
+        train_dataset, test_dataset = ns["random_split"](Dataset, [train_size, test_size])
         self.train_loader = ns["DataLoader"](train_dataset, batch_size=batch_size, shuffle=True)
+        self.test_loader = ns["DataLoader"](test_dataset, batch_size=batch_size, shuffle=False)
+        self.test_size, self.batch_size, self.ns = test_size, batch_size, ns
         Scount, Rcount = Dataset.get_count()
+        self.Rcount = Rcount
         inter_adj, city_adj, province_adj = Dataset.get_adjacent()
         nrm = ns["normalize_adjacency_matrix"]
         inter_adj = nrm(inter_adj)
@@ -127,3 +132,72 @@ class TrainPy:
         loss_train.backward()
         self.optimizer.step()
         return loss
+
+    def test_epoch(self, device_metrics):
+        """train.py's ``test()`` over the test split; returns what train.py:273-282 prints
+        as a dict (loss, auc, accuracy, precision / recall / f1, macro and micro).
+
+        ``device_metrics=False`` replays train.py:239-272 statement for statement: a
+        ``.cpu().item()`` per predicted label and per true label, a ``.cpu().numpy()`` per
+        prediction row, then ``metrics.py``'s sklearn functions.  ``True`` runs the same
+        loop with ``metrics.Evaluator``: one launch per batch and two small reads at the
+        end.  The model is back in training mode afterwards (train.py:219 puts it there at
+        the top of the next epoch)."""
+        ns, model, device = self.ns, self.model, self.device
+        inter_adj, city_adj, province_adj = self.inter_adj, self.city_adj, self.province_adj
+        np, F = ns["np"], self.F
+        model.eval()
+        try:
+            if device_metrics:
+                from .metrics import Evaluator
+
+                ev = Evaluator(self.Rcount, self.test_size, device)
+                with torch.no_grad():
+                    for i, data in enumerate(self.test_loader, 0):
+                        source_index, recipient_index = data
+                        source_index = source_index.to(device)
+                        recipient_index = recipient_index.to(device)
+                        output = model(inter_adj, city_adj, province_adj, source_index)
+                        ev.update(output, source_index, recipient_index)
+                m = ev.compute(batch_size=self.batch_size)
+                return {k: m[k] for k in ("loss", "auc", "accuracy", "precision_macro",
+                                          "recall_macro", "f1_macro", "precision_micro",
+                                          "recall_micro", "f1_micro")}
+            y_pred_test = []
+            y_true_test = []
+            y_preds = []
+            Loss_test = 0
+            with torch.no_grad():
+                for i, data in enumerate(self.test_loader, 0):
+                    source_index, recipient_index = data
+                    source_index = source_index.to(device)
+                    recipient_index = recipient_index.to(device)
+                    output = model(inter_adj, city_adj, province_adj, source_index)
+                    loss_test = F.nll_loss(output[source_index], recipient_index)
+                    Loss_test += loss_test.item()
+
+                    preds = output[source_index]
+                    pred_label = preds.max(1)[1].type_as(recipient_index)
+                    for tag in pred_label:
+                        y_preds.append(tag.cpu().item())
+                    for pred in preds:
+                        y_pred_test.append(pred.detach().cpu().numpy().tolist())
+                    for t in recipient_index:
+                        y_true_test.append(t.cpu().item())
+                y_preds = np.array(y_preds)
+                y_pred_test = np.array(y_pred_test)
+                y_true_test = np.array(y_true_test)
+                auc_test = ns["calculate_auc"](y_pred_test, y_true_test)
+                acc = ns["calculate_accuracy"](y_preds, y_true_test)
+                precision_macro, recall_macro = ns["calculate_precision_recall"](
+                    y_preds, y_true_test, 'macro')
+                f1_macro = 2 * (precision_macro * recall_macro) / (precision_macro + recall_macro)
+                precision_micro, recall_micro = ns["calculate_precision_recall"](
+                    y_preds, y_true_test, 'micro')
+                f1_micro = 2 * (precision_micro * recall_micro) / (precision_micro + recall_micro)
+            return {"loss": Loss_test / len(self.test_loader), "auc": auc_test, "accuracy": acc,
+                    "precision_macro": precision_macro, "recall_macro": recall_macro,
+                    "f1_macro": f1_macro, "precision_micro": precision_micro,
+                    "recall_micro": recall_micro, "f1_micro": f1_micro}
+        finally:
+            model.train()
