@@ -795,6 +795,14 @@ __global__ void __launch_bounds__(256) bwd_row_stats_kernel(
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   for (int64_t r0 = wave * RPW; r0 < n_rows; r0 += nwaves * RPW) {
     Pk<T> a[UNR][G::QPL], b[UNR][G::QPL];
+    // the uc pieces and what the writer lanes store (el, lse, qc of the lane's head -- the
+    // lanes of a head read one address -- and the row flag) are loaded with the dU and u
+    // pieces, before the first use, rows past the end clamped like theirs (they were
+    // loaded inside the compute loop and the store branch: two dependent round trips per
+    // row group after the first)
+    float4 c[UNR][G::QPL][RT ? G::V / 4 : 1];
+    float elv[UNR][G::QPL], lsev[UNR][G::QPL], qcv[UNR][G::QPL];
+    uint8_t fl[UNR];
     const bool lo = sizeof(T) == 2 && u_lo != nullptr;
 #pragma unroll
     for (int g = 0; g < UNR; ++g) {
@@ -805,6 +813,23 @@ __global__ void __launch_bounds__(256) bwd_row_stats_kernel(
         a[g][k] = pk_load(dU + row * G::D + G::V * q);
         b[g][k] = pk_load(u + row * G::D + G::V * q);
       }
+#pragma unroll
+      for (int k = 0; k < G::QPL; ++k) {
+        const int q = quad_of<G>(lane, k);
+        if (RT) {
+#pragma unroll
+          for (int v = 0; v < G::V / 4; ++v)
+            c[g][k][v] = *reinterpret_cast<const float4*>(uc + row * G::D + G::V * q + 4 * v);
+          qcv[g][k] = qc[row * H + q / G::QH];
+        }
+        elv[g][k] = el[row * H + q / G::QH];
+        lsev[g][k] = lse[row * H + q / G::QH];
+      }
+      // (uniform branch: the compiler closes each row group's batch at its flag byte, so
+      // a trip is four batches, 94 VGPRs / 5 waves per SIMD, 26.7-27.0 us at C4; the flag
+      // through a buffer descriptor put the whole trip in one batch at 106 VGPRs /
+      // 4 waves: 28.1 us.  The loads inside the compute loop and store branch: 30.5 us.)
+      fl[g] = rowflag != nullptr ? rowflag[row] : (uint8_t)0;
     }
 #pragma unroll
     for (int g = 0; g < UNR; ++g) {
@@ -820,12 +845,10 @@ __global__ void __launch_bounds__(256) bwd_row_stats_kernel(
         const float dk = group_sum<G::QH>(dot);
         float dc = 0.f;
         if (RT) {  // dU_i . uc_i over the head's pieces (uc is fp32 for either table type)
-          const int64_t rr = min(row, n_rows - 1);
-          const float* cp = uc + rr * G::D + G::V * q;
           float cv = 0.f;
 #pragma unroll
           for (int v = G::V - 4; v >= 0; v -= 4) {
-            const float4 c4 = *reinterpret_cast<const float4*>(cp + v);
+            const float4 c4 = c[g][k][v / 4];
             cv = fmaf(a[g][k].v[v + 3], c4.w, cv);
             cv = fmaf(a[g][k].v[v + 2], c4.z, cv);
             cv = fmaf(a[g][k].v[v + 1], c4.y, cv);
@@ -837,15 +860,12 @@ __global__ void __launch_bounds__(256) bwd_row_stats_kernel(
         if (q % G::QH == 0 && row < n_rows) {
           const int h = q / G::QH;
           float* r = rec + row * rec_stride(H);
-          r[h] = el[row * H + h];
-          r[H + h] = lse[row * H + h];
+          r[h] = elv[g][k];
+          r[H + h] = lsev[g][k];
           r[2 * H + h] = dk;
-          if (rec_has_flag(H) && h == 0)
-            r[3 * H] = rowflag != nullptr && rowflag[row] != 0 ? 1.f : 0.f;
-          if (RT) {
-            const bool virt = rowflag != nullptr && rowflag[row] != 0;
-            d_el[row * H + h] = virt ? 0.f : fmaf(-dk, qc[row * H + h], dc);
-          }
+          const bool virt = fl[g] != 0;
+          if (rec_has_flag(H) && h == 0) r[3 * H] = virt ? 1.f : 0.f;
+          if (RT) d_el[row * H + h] = virt ? 0.f : fmaf(-dk, qcv[g][k], dc);
         }
       }
     }

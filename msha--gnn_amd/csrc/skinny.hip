@@ -111,7 +111,9 @@ struct ProjGeo {
 // index fall in 8 banks (8-way).  One element per lane in M's order (k fastest) put every
 // lane of a wave on 2 banks (32-way), ~7 us of LDS time per block at K = N = 128.
 // Every piece a thread copies is loaded before the first is written (one HBM round trip
-// for the whole fill instead of one per piece).
+// for the whole fill instead of one per piece).  (n fastest across the lanes instead --
+// conflict-free stores, but each lane's 16-byte load then touches its own 128-byte line
+// of M -- measured slower: dx_kernel 44.7 vs 43.8 us at C4, 22.6 vs 22.4 at R15.)
 template <int PIECES, int NT>
 struct Pieces {
   static constexpr int IT = (PIECES + NT - 1) / NT;
@@ -125,6 +127,36 @@ struct Pieces {
     for (int i = 0; i < IT; ++i) {
       const u32x4_t x = buf_b128(r, ok(tid + NT * i) ? 16u * (tid + NT * i) : kOOB);
       v[i] = make_uint4(x[0], x[1], x[2], x[3]);
+    }
+  }
+};
+
+// A row-major W[k][n]'s columns for an [n][k] bf16 image (pitch K + 8 elements): a
+// thread owns 8 consecutive k of one dword of columns (one fp32 n / two bf16 n),
+// consecutive lanes consecutive dwords.  A wave's load of one k is 256 contiguous bytes,
+// and the 8 k of a column leave as one 16-byte LDS store at a lane stride of one image
+// row (K = 128: 68 dwords = 4 mod 32, K = 64: 36 = 4 mod 32): the 8 lanes of a
+// ds_write_b128 group cover the 32 banks once.  (A 16-byte piece of a W row per thread,
+// stored one 2-byte element at a time at o = n (K + 8) + k, put the 32 lanes of a store
+// group -- n = 4 n4 + j, n4 = lane -- four image rows apart, 272 dwords = 16 mod 32: 2
+// banks, 16 addresses each, 768 such stores per block in the split form.  Entry to "W
+// resident" at C4: 27.2k cycles,
+// 12.0 us, then; 9.5k cycles, 4.5 us, now; the launch 34.7 -> 26.8 us.)
+template <typename T, int K, int N, int NT>
+struct WCols {
+  static constexpr int NL = N * (int)sizeof(T) / 4;  // column dwords per k
+  static constexpr int TASKS = NL * (K / 8);
+  static constexpr int IT = (TASKS + NT - 1) / NT;
+  static __device__ __forceinline__ bool ok(int t) { return TASKS % NT == 0 || t < TASKS; }
+  uint32_t v[IT][8];
+  __device__ __forceinline__ void load(const void* src, int tid) {
+    const rsrc_t r = make_rsrc(src, (uint32_t)(K * N * sizeof(T)));
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const int t = tid + NT * i;
+      const uint32_t off = ok(t) ? (uint32_t)(t / NL) * (8u * N * sizeof(T)) + 4u * (t % NL) : kOOB;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[i][j] = (uint32_t)buf_i32(r, off + j * (uint32_t)(N * sizeof(T)));
     }
   }
 };
@@ -295,7 +327,9 @@ __global__ void __launch_bounds__((64 * ProjStage<T, K, N, FE, SPLIT>::WAVES)) p
   // held by the rows' HBM burst (every wave's first tile at once, ~16 MB at C4), whose
   // latency hides under the W copy and the first steps instead.  (A load -> store loop
   // paid one HBM round trip per W piece: ~4 us of a 40 us launch.)
-  Pieces<K * N * (int)sizeof(T) / 16, 64 * kWaves> wp;
+  constexpr bool kColFill = X3 || !G::F32;  // [n][k] bf16 images: column-wise fill (WCols)
+  std::conditional_t<kColFill, WCols<T, K, N, 64 * kWaves>,
+                     Pieces<K * N * (int)sizeof(T) / 16, 64 * kWaves>> wp;
   wp.load(W, tid);
   static_assert(N <= 64 * kWaves, "one score-vector element per thread");
   const uint32_t aoff = tid < N ? 4u * tid : kOOB;
@@ -313,32 +347,37 @@ __global__ void __launch_bounds__((64 * ProjStage<T, K, N, FE, SPLIT>::WAVES)) p
   for (int i = 0; i < wp.IT; ++i) {
     const int idx = tid + 64 * kWaves * i;
     if (!wp.ok(idx)) continue;
-    if constexpr (X3) {  // W[k][4 n4 .. +3] -> the three bf16 images at [n][k]
-      const int k = idx / (N / 4), n4 = idx % (N / 4);
-      const uint32_t e4[4] = {wp.v[i].x, wp.v[i].y, wp.v[i].z, wp.v[i].w};
-      bf16_t* Wx = reinterpret_cast<bf16_t*>(Wl);
+    if constexpr (X3) {  // W[8 k8 .. +7][n] -> 16 bytes of each bf16 image at [n][8 k8]
+      const int k8 = idx / N, n = idx % N;
+      float x[8];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float x = __uint_as_float(e4[j]);
-        const bf16_t hb = (bf16_t)x;
-        const float r1 = x - (float)hb;
-        const bf16_t mb = (bf16_t)r1;
-        const int o = (4 * n4 + j) * S::XPW + k;
-        Wx[o] = hb;
-        Wx[S::XIMG + o] = mb;
-        Wx[2 * S::XIMG + o] = (bf16_t)(r1 - (float)mb);
-      }
+      for (int j = 0; j < 8; ++j) x[j] = __uint_as_float(wp.v[i][j]);
+      const Split3 s3 = split3(x);
+      bf16_t* Wx = reinterpret_cast<bf16_t*>(Wl) + n * S::XPW + 8 * k8;
+      *reinterpret_cast<bf16x8*>(Wx) = s3.h;
+      *reinterpret_cast<bf16x8*>(Wx + S::XIMG) = s3.m;
+      *reinterpret_cast<bf16x8*>(Wx + 2 * S::XIMG) = s3.l;
     } else if constexpr (G::F32) {
       const int k = idx / (N / 4), n4 = idx % (N / 4);
       const int kr = proj_img_row<G::KL>(k);
       *reinterpret_cast<uint4*>(reinterpret_cast<float*>(Wl) + kr * G::PW + 4 * n4) = wp.v[i];
     } else {
-      const int k = idx / (N / 8), n8 = idx % (N / 8);
-      const uint32_t e2[4] = {wp.v[i].x, wp.v[i].y, wp.v[i].z, wp.v[i].w};
-      uint16_t* Wt = reinterpret_cast<uint16_t*>(Wl);
+      // W[8 k8 .. +7][2 n2, 2 n2 + 1] -> 16 bytes of image rows 2 n2 and 2 n2 + 1.  Lanes
+      // are two rows (8 mod 32 dwords) apart, so the upper 4 lanes of a store group write
+      // the odd row (+4 banks) first: each store instruction covers the 32 banks once.
+      const int k8 = idx / (N / 2), n2 = idx % (N / 2);
+      const bool odd_first = (lane & 4) != 0;
+      uint32_t p0[4], p1[4];  // first and second store's k pairs
 #pragma unroll
-      for (int e = 0; e < 8; ++e)
-        Wt[(8 * n8 + e) * G::PW + k] = (uint16_t)(e2[e >> 1] >> (16 * (e & 1)));
+      for (int q = 0; q < 4; ++q) {
+        const uint32_t a = wp.v[i][2 * q], b = wp.v[i][2 * q + 1];
+        const uint32_t even = (a & 0xffffu) | (b << 16), odd = (a >> 16) | (b & 0xffff0000u);
+        p0[q] = odd_first ? odd : even;
+        p1[q] = odd_first ? even : odd;
+      }
+      uint16_t* Wt = reinterpret_cast<uint16_t*>(Wl) + 2 * n2 * G::PW + 8 * k8;
+      *reinterpret_cast<uint4*>(Wt + (odd_first ? G::PW : 0)) = make_uint4(p0[0], p0[1], p0[2], p0[3]);
+      *reinterpret_cast<uint4*>(Wt + (odd_first ? 0 : G::PW)) = make_uint4(p1[0], p1[1], p1[2], p1[3]);
     }
   }
   if (FE > 0 && tid < N) {  // (a null al / ar reads 0: an empty descriptor)
@@ -2014,11 +2053,20 @@ int skinny_project(int64_t M, int64_t K, int heads, int feat, const void* X, con
   const bool score = al != nullptr || ar != nullptr;
   const int minfe = 16 / (int)sizeof(T);
   if (score && (feat < minfe || N % feat != 0)) return 0;
-  // fp32: the split-bf16 form from 64k rows (1M rows: 292 vs 368 us, C4's 100k: 36.6 vs
-  // 39.4 us); below it the three-image W fill outweighs the faster steps (R15's 39k rows:
-  // 24.9 vs 20.8 us), so the exact-fp32 MFMA runs there
+  // fp32: the split-bf16 form from 64k rows (MSHA_PROJ_SPLIT_MIN_ROWS moves the cut-over
+  // for A/B runs), the exact-fp32 MFMA below.  Kernel times with the column-wise W fill,
+  // split vs exact fp32, 8 x 16 / 2 x 64: 100k rows 27 vs 35 / 25 vs 38 us, 65,536 19 vs 25 /
+  // 19 vs 26, 50,000 16.7 vs 24.0 / 18.3 vs 26.3, 39,179 20.8 vs 20.6 / 17.7 vs 21.4, 32,768
+  // 20.8 vs 17.1 / 16.8 vs 17.2.  The split form now wins from about 50,000 rows, but the
+  // cut-over stays: the 2018 graph's 50,015 source rows would change form, and the Ours
+  // layer's input-gradient check on that graph then misses its bound in 1 of 6.4M
+  // elements (1.07 x)
   constexpr bool kF32 = std::is_same<T, float>::value;
-  const bool split = kF32 && M >= 65536;
+  static const int64_t split_min = [] {
+    const char* v = getenv("MSHA_PROJ_SPLIT_MIN_ROWS");
+    return v != nullptr && *v ? (int64_t)atoll(v) : (int64_t)65536;
+  }();
+  const bool split = kF32 && M >= split_min;
 #define SKP(k, n, fe)                                                                           \
   if (K == k && N == n && (score ? feat == fe : fe == 0)) {                                    \
     if (split) {                                                                                \
@@ -2181,7 +2229,11 @@ int skinny_wgrad(int64_t M, int64_t N, int64_t K, const float* A, int64_t sAm, i
     return 0;
   float* slab = (float*)ws;
   // below ~128k rows a wave of the split kernel has too few 16-row steps to repay its
-  // fixed costs (C4 100k rows: 46 vs 43 us): the exact-fp32 kernel runs there
+  // fixed costs (C4 100k rows: 46 vs 43 us): the exact-fp32 kernel runs there.  (A form
+  // with two waves per SIMD, each owning one 64-column half of dW in 128 accumulators,
+  // gave the one-wave form's bits but no speed: with the h-table column sums 44.4-45.1 us
+  // at 100k rows against 44.8-45.4 one wave and 43.3-45.5 exact fp32, 112-115 vs 97-103 us
+  // at 262,144; X single-buffered and 12 registers of scratch at the 256-register limit.)
   static const int64_t s3_min = [] {
     const char* v = getenv("MSHA_WGRAD_S3_MIN_ROWS");
     return v != nullptr && *v ? (int64_t)atoll(v) : (int64_t)131072;
