@@ -839,6 +839,71 @@ MSHA_API int msha_rank_auc(int64_t n, int32_t C, const float* scores, int64_t ld
 /* host-only: the largest n the one-block LDS path takes (ABI 16, added) */
 MSHA_API int64_t msha_rank_auc_block_keys(void);
 
+/* ---- Top-K link retrieval for the inner-product scorer (LLP.py:20 Hits@K,
+ * Explainer.py:31-34) (ABI 16, added) ---------------------------------------------------
+ * For query position b in [0, n_q): the k candidates j in [0, n_cand) with the highest
+ * logit sum_f Q[q, f] * T[j, f], q = qi[b] (qi NULL: b), accumulated in fp32 on the matrix
+ * cores (fp32 tables: the exact-f32 MFMA, an fma chain; bf16 tables: the bf16 MFMA), in an
+ * order fixed by f alone: a candidate's logit does not depend on the tile, block or split
+ * that computed it.  The (n_q, n_cand) score matrix is never written.
+ *
+ * Order: logit descending, then candidate index ascending -- a total order, so the result
+ * is unique.  Logits compare through the order-preserving uint32 image of msha_rank_auc
+ * (-0.0 folded onto +0.0); +inf ranks first, every NaN below -inf, NaNs among themselves
+ * by index.
+ *
+ * out_val / out_idx: (n_q, k) fp32 / int64, each row best first.  out_idx = j + col_offset
+ * (a shard reports global rows); out_val = the logit, or 1 / (1 + exp(-logit)) with
+ * sigmoid != 0 -- the ranking is by the logit either way.  Slots past the number of
+ * available candidates hold -inf (0.0 under sigmoid) and index -1.
+ *
+ * A qi[b] outside [0, rows_q) makes row b all filler and sets *err (nullable) to 1;
+ * nothing is read through it.  excl_rowptr (int32, n_q + 1) / excl_col (int32, ascending
+ * within a row, candidate-local numbering), both or neither: candidates never returned
+ * for query POSITION b.
+ *
+ * splits: column splits of the candidate range (0: msha_topk_inner_splits); each split
+ * writes a partial list into ws and a merge launch combines them; the result does not
+ * depend on it.  ws: msha_topk_inner_workspace_size bytes, 16-byte aligned, contents
+ * irrelevant.  Q, T: 16-byte aligned, row pitches ldq / ldt elements, multiples of 16
+ * bytes; Q may be T.  feat a multiple of 16 in [16, 256], 1 <= k <= 128, n_cand < 2^31 - 1
+ * (msha_topk_inner_supported); n_q = 0 launches nothing, n_cand = 0 only the filler.
+ * Stateless; integer compares and ordinary stores only, no float atomics. */
+/* host-only (ABI 16, added) */
+MSHA_API int msha_topk_inner_supported(int32_t feat, int32_t k, int32_t dtype);
+/* bytes of ws for msha_topk_inner; splits 0: for the default split count (ABI 16, added) */
+MSHA_API size_t msha_topk_inner_workspace_size(int64_t n_q, int64_t n_cand, int32_t k,
+                                               int32_t splits);
+/* host-only: the default split count -- one block per CU from query tiles x splits, at
+ * least 512 candidates per split; 1 when the query tiles alone fill the device
+ * (ABI 16, added) */
+MSHA_API int msha_topk_inner_splits(int64_t n_q, int64_t n_cand, int32_t feat, int32_t k,
+                                    int32_t dtype);
+/* the retrieval itself, as described above (ABI 16, added) */
+MSHA_API int msha_topk_inner(int64_t n_q, int32_t feat, int32_t dtype, const void* Q,
+                             int64_t ldq, const int64_t* qi, int64_t rows_q, const void* T,
+                             int64_t ldt, int64_t n_cand, int64_t col_offset,
+                             const int32_t* excl_rowptr, const int32_t* excl_col, int32_t k,
+                             int32_t sigmoid, int32_t splits, float* out_val, int64_t* out_idx,
+                             int32_t* err, void* ws, size_t ws_bytes, msha_stream_t stream);
+/* Top k of `rows` rows of lists * len candidates under the same order and filler rule
+ * (ABI 16, added): vals (rows, lists * len) fp32, idx the candidates' int64 indices in
+ * [0, 2^32 - 1) -- an entry with idx < 0 is ignored -- or NULL: the position in the row.
+ * The lists need not be sorted.  sigmoid != 0: out_val = 1 / (1 + exp(-value)) of the
+ * selected values (lists of logits; the order is by the value given).  The second stage
+ * of msha_topk_inner's column splits, the cross-rank merge of sharded lists, and on a
+ * plain score vector (rows = 1, lists = 1) the selection behind hits@k.  A row longer than
+ * 4096 is cut into chunks, each selected by
+ * one wave, and the selections merged again through ws
+ * (msha_topk_merge_workspace_size bytes, 16-byte aligned, contents irrelevant).
+ * 1 <= k <= 128, lists * len < 2^32 - 1. */
+MSHA_API size_t msha_topk_merge_workspace_size(int64_t rows, int64_t lists, int64_t len,
+                                               int32_t k); /* (ABI 16, added) */
+MSHA_API int msha_topk_merge(int64_t rows, int64_t lists, int64_t len, int32_t k,
+                             const float* vals, const int64_t* idx, int32_t sigmoid,
+                             float* out_val, int64_t* out_idx, void* ws, size_t ws_bytes,
+                             msha_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,14 @@ SIGNATURES = {
     "msha_rank_auc_workspace_size": (SZ, [I64, I32]),
     "msha_rank_auc": (C.c_int, [I64, I32, P, I64, P, P, I32, P, P, SZ, P]),
     "msha_rank_auc_block_keys": (I64, []),
+    # top-K link retrieval (ABI 16, added)
+    "msha_topk_inner_supported": (C.c_int, [I32, I32, I32]),
+    "msha_topk_inner_workspace_size": (SZ, [I64, I64, I32, I32]),
+    "msha_topk_inner_splits": (C.c_int, [I64, I64, I32, I32, I32]),
+    "msha_topk_inner": (C.c_int, [I64, I32, I32, P, I64, P, I64, P, I64, I64, I64, P, P, I32,
+                                  I32, I32, P, P, P, P, SZ, P]),
+    "msha_topk_merge_workspace_size": (SZ, [I64, I64, I64, I32]),
+    "msha_topk_merge": (C.c_int, [I64, I64, I64, I32, P, P, I32, P, P, P, SZ, P]),
 }
 
 _lib = None

@@ -1092,6 +1092,141 @@ def score_pairs(h, src, dst, mode="inner", W=None, b=None, out=None, out_dtype=N
     return out
 
 
+# ------------------------------------------------------- top-K link retrieval ---
+TOPK_MAX_K = 128
+
+
+def exclude_from_pairs(q_pos, cols, n_q: int):
+    """The ``exclude`` argument of ``topk_inner`` from unsorted (query position, column)
+    pair lists: ``(rowptr, col)`` int32, CSR over the ``n_q`` query positions, columns
+    ascending within a row, duplicates dropped.  torch sorts on the lists' device (the
+    number of distinct pairs is read back: one sync)."""
+    q_pos = q_pos.to(torch.int64).reshape(-1)
+    cols = cols.to(torch.int64).reshape(-1)
+    if q_pos.numel() != cols.numel():
+        raise ValueError(f"pair lists differ in length: {q_pos.numel()} vs {cols.numel()}")
+    key = torch.unique((q_pos << 31) | cols)  # sorted: by position, then by column
+    counts = torch.bincount(key >> 31, minlength=int(n_q))
+    if counts.numel() != int(n_q):
+        raise IndexError(f"a query position is outside [0, {int(n_q)})")
+    rowptr = torch.zeros(int(n_q) + 1, dtype=torch.int64, device=key.device)
+    rowptr[1:] = torch.cumsum(counts, 0)
+    return rowptr.to(torch.int32), (key & 0x7FFFFFFF).to(torch.int32)
+
+
+def _topk_k(k) -> int:
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+    return k
+
+
+def topk_inner(q, table, k, rows=None, exclude=None, sigmoid=True, col_offset=0, splits=None,
+               check=True):
+    """For each query the ``k`` rows of ``table`` with the highest inner product, without
+    the (B, n) score matrix: ``(values, indices)``, (B, k) float32 / int64, each row best
+    first.  Query b is ``q[rows[b]]`` (``rows`` None: ``q[b]``); ``q`` may be ``table``.
+    ``q`` and ``table`` share dtype (float32: exact-f32 MFMA; bfloat16: bf16 MFMA, fp32
+    accumulation) and feature width (a multiple of 16 up to 256).
+
+    Order: logit descending, then index ascending (unique; +inf first, NaN below -inf).
+    ``values`` are the probabilities 1 / (1 + exp(-logit)), or the logits with
+    ``sigmoid=False``; the ranking is by the logit either way.  ``indices`` are
+    ``row + col_offset``; slots past the available candidates hold -inf (0.0 under
+    ``sigmoid``) and -1.  ``exclude``: ``(rowptr, col)`` int32 tensors
+    (``exclude_from_pairs``), candidates never returned for query position b.
+    ``splits``: column splits (None: the library's default); the result does not depend
+    on it.
+
+    ``check`` (default) applies torch's ``q[rows]`` rule first (``check_pair_indices``:
+    IndexError outside [-n, n), negatives wrapped; one stream sync).  With ``check=False``
+    the caller vouches for ``rows`` in [0, n): no host sync happens (the call can be
+    captured into a HIP graph), and the kernel still bounds every row -- a stray one comes
+    back as filler.  Inference only: the outputs are detached."""
+    if q.dtype != table.dtype:
+        raise TypeError(f"q and table must share a dtype, got {q.dtype} and {table.dtype}")
+    if q.dtype not in (torch.float32, BF16):
+        raise TypeError("topk_inner takes float32 or bfloat16 tables")
+    if q.dim() != 2 or table.dim() != 2 or q.shape[1] != table.shape[1]:
+        raise ValueError(f"q and table must be 2-D with one feature width, got "
+                         f"{tuple(q.shape)} and {tuple(table.shape)}")
+    k = _topk_k(k)
+    Fd = q.shape[1]
+    code = _code(q.dtype)
+    _lib.require_cuda(q, table, rows)
+    if not _lib.fn("msha_topk_inner_supported")(Fd, k, code):
+        raise ValueError(f"topk_inner: feature width {Fd} must be a multiple of 16 in [16, 256]")
+    q, table = q.detach(), table.detach()
+    esz = q.element_size()
+
+    def aligned(t):
+        return (t.stride(1) == 1 and (t.stride(0) * esz) % 16 == 0 and t.stride(0) >= Fd
+                and t.data_ptr() % 16 == 0)
+
+    if not aligned(q):
+        q = q.contiguous()
+    if not aligned(table):
+        table = table.contiguous()
+    dev = q.device
+    if rows is not None:
+        if check:
+            rows, _ = check_pair_indices(rows, rows, q.shape[0])
+        rows = rows.to(torch.int64).contiguous()
+        B = rows.numel()
+    else:
+        B = q.shape[0]
+    rp = cp = None
+    if exclude is not None:
+        rp, cp = exclude
+        _lib.require_cuda(rp, cp)
+        if rp.dtype != torch.int32 or cp.dtype != torch.int32 or rp.numel() != B + 1:
+            raise ValueError("exclude must be (rowptr, col) int32 tensors with B + 1 row "
+                             "pointers (exclude_from_pairs)")
+        rp, cp = rp.contiguous(), cp.contiguous()
+        if cp.numel() == 0:  # a NULL column list would read as "no exclusion half given"
+            rp = cp = None
+    n = table.shape[0]
+    splits = 0 if splits is None else int(splits)
+    vals = torch.empty(B, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(B, k, dtype=torch.int64, device=dev)
+    need = _lib.fn("msha_topk_inner_workspace_size")(B, n, k, splits)
+    ws = _workspace(dev, need)
+    _lib.call("msha_topk_inner", B, Fd, code, q.data_ptr(), q.stride(0), _lib.ptr(rows),
+              q.shape[0], table.data_ptr() if n else None, table.stride(0), n, int(col_offset),
+              _lib.ptr(rp), _lib.ptr(cp), k, 1 if sigmoid else 0, splits, vals.data_ptr(),
+              idx.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream(q))
+    return vals, idx
+
+
+def topk_merge(vals, idx=None, k=1, sigmoid=False):
+    """Top ``k`` of each row of candidate lists under ``topk_inner``'s order: ``vals``
+    (rows, lists, len) or (rows, n) float32, ``idx`` int64 of the same shape (entries < 0
+    are ignored) or None (the position in the row).  Returns (rows, k) values and indices,
+    filler -inf (0.0 under ``sigmoid``) / -1.  ``sigmoid`` maps the selected values (lists
+    of logits) to probabilities; the order is by the values given.  The cross-rank merge
+    of ``sharding.topk_sharded`` and the selection behind ``metrics.hits_at_k``; rows of
+    any length (cut into chunks and merged hierarchically)."""
+    k = _topk_k(k)
+    _lib.require_cuda(vals, idx)
+    if vals.dim() not in (2, 3):
+        raise ValueError("vals must be (rows, lists, len) or (rows, n)")
+    if idx is not None and idx.shape != vals.shape:
+        raise ValueError("idx must have the shape of vals")
+    rows = vals.shape[0]
+    lists, ln = (vals.shape[1], vals.shape[2]) if vals.dim() == 3 else (1, vals.shape[1])
+    v = vals.detach().to(torch.float32).contiguous()
+    i = idx.to(torch.int64).contiguous() if idx is not None else None
+    dev = v.device
+    out_v = torch.empty(rows, k, dtype=torch.float32, device=dev)
+    out_i = torch.empty(rows, k, dtype=torch.int64, device=dev)
+    need = _lib.fn("msha_topk_merge_workspace_size")(rows, lists, ln, k)
+    ws = _workspace(dev, need)
+    _lib.call("msha_topk_merge", rows, lists, ln, k, v.data_ptr() if v.numel() else None,
+              _lib.ptr(i) if i is not None and i.numel() else None, 1 if sigmoid else 0,
+              out_v.data_ptr(), out_i.data_ptr(), ws.data_ptr(), ws.numel(), _stream(v))
+    return out_v, out_i
+
+
 # --------------------------------------------------------- full MSHA layer (Ours) ---
 # the bipartite kernels' block-partial reduce rides in the Ours layer's prep / finish
 # launches (msha_bip_defer_reduce; one graph node fewer each way); MSHA_BIP_DEFER=0: separate

@@ -324,6 +324,19 @@ class LinkPredictor(torch.nn.Module):
             return self.forward(h[src], h[dst])
         return MF.score_pairs(h, src, dst, "mlp", self.lins[0].weight, self.lins[0].bias)
 
+    def topk(self, h, src, k, candidates=None, exclude=None):
+        """The ``k`` most probable links of each ``h[src[b]]`` among the rows of
+        ``candidates`` (default: ``h`` itself): (probabilities, indices into
+        ``candidates``), (B, k) each, best first (``functional.topk_inner``; the (B, n)
+        score matrix is never built).  'inner' only: the reference's 'mlp' head returns a
+        (B, hidden) vector per pair (LLP.py:107-111), which gives no scalar to rank by."""
+        if self.predictor != "inner":
+            raise ValueError(f"LinkPredictor.topk needs the 'inner' predictor: "
+                             f"{self.predictor!r} scores a pair with a vector (LLP.py:107-115), "
+                             f"so there is no scalar to rank by")
+        return MF.topk_inner(h, h if candidates is None else candidates, k, rows=src,
+                             exclude=exclude, sigmoid=True)
+
 
 class OursLayer(OursLayer3):
     """Ours.py:29-109: OursLayer3's inter attention plus the intra-source attention

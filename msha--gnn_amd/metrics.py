@@ -238,3 +238,38 @@ def binary_auc(scores, labels):
     y = labels.to(torch.int64).contiguous()
     counts = _rank_auc(s, s.shape[0], 1, 1, y, None, True, {})
     return auc_from_counts(counts.cpu().numpy())
+
+
+def hits_at_k(pos, neg, k):
+    """Hits@K of link scores, the OGB definition: the fraction of ``pos`` scores strictly
+    greater than the K-th largest ``neg`` score; 1.0 with fewer than K negatives.  ``pos``
+    and ``neg``: score vectors on the device, float32 or bfloat16 (widened exactly).  The
+    K-th largest negative is selected on the device (``msha_topk_merge``, hierarchically
+    for long vectors); only the final count comes to the host (one read).  NaN if a score
+    is not finite; ValueError on an empty ``pos``."""
+    import torch
+
+    from . import _lib as L
+    from . import functional as MF
+
+    L.require_cuda(pos, neg)
+    if pos.dim() != 1 or neg.dim() != 1:
+        raise ValueError("pos and neg must be score vectors")
+    for s in (pos, neg):
+        if s.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("scores must be float32 or bfloat16")
+    if pos.numel() == 0:
+        raise ValueError("no positive scores")
+    k = int(k)
+    if not 1 <= k <= MF.TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {MF.TOPK_MAX_K}]")
+    p = pos.detach().to(torch.float32)
+    n = neg.detach().to(torch.float32).contiguous()
+    bad = (~torch.isfinite(p)).any() | (~torch.isfinite(n)).any()
+    if n.numel() < k:
+        hits = torch.full((), p.numel(), dtype=torch.int64, device=p.device)
+    else:
+        kth = MF.topk_merge(n.view(1, -1), None, k)[0][0, k - 1]
+        hits = (p > kth).sum()
+    hits, bad = torch.stack([hits, bad.to(torch.int64)]).tolist()
+    return float("nan") if bad else hits / p.numel()

@@ -120,6 +120,49 @@ def score_sharded(table: ShardedTable, src: torch.Tensor, dst: torch.Tensor, sco
     return lo, hi, score_fn(h, src[lo:hi], dst[lo:hi])
 
 
+def _local_exclude(exclude, lo: int, hi: int):
+    """The part of a global-column exclusion CSR inside [lo, hi), renumbered from lo."""
+    rowptr, col = exclude
+    B = rowptr.numel() - 1
+    counts = (rowptr[1:] - rowptr[:-1]).to(torch.int64)
+    pos = torch.repeat_interleave(torch.arange(B, device=col.device), counts)
+    keep = (col >= lo) & (col < hi)
+    kept = torch.bincount(pos[keep], minlength=B)
+    rp = torch.zeros(B + 1, dtype=torch.int64, device=col.device)
+    rp[1:] = torch.cumsum(kept, 0)
+    return rp.to(torch.int32), (col[keep] - lo).to(torch.int32)
+
+
+def topk_sharded(table: ShardedTable, q: torch.Tensor, k: int, topk_fn, merge_fn, exclude=None):
+    """Top-k retrieval against a sharded table WITHOUT gathering it: every rank ranks the
+    replicated queries ``q`` (B, F) against its own rows only (the last shard's padding
+    rows are not candidates), ``topk_fn(q, local_rows, k, exclude, col_offset)`` ->
+    ((B, k) values, (B, k) global indices, -1: none); ONE all-gather of the (B, k) value
+    and index lists follows, and ``merge_fn(values (B, world, k), indices, k)`` runs on
+    every rank.  ``exclude``: ``(rowptr, col)`` with GLOBAL column numbers; each rank keeps
+    and renumbers its own range.  For the ranking to be by the logit, ``topk_fn`` returns
+    logits (``functional.topk_inner(..., sigmoid=False)``) and ``merge_fn`` maps the
+    winners (``functional.topk_merge(..., sigmoid=True)``).  Without a process group and
+    world 1 this is the local call."""
+    lo, hi = row_range(table.n, table.world, table.rank)
+    ex = _local_exclude(exclude, lo, hi) if exclude is not None else None
+    vals, idx = topk_fn(q, table.local[: hi - lo], k, ex, lo)
+    path = table.path()
+    W, B = table.world, vals.shape[0]
+    if path == "copy":
+        return merge_fn(vals.reshape(B, 1, k), idx.reshape(B, 1, k), k)
+    # one collective: the fp32 values ride as their bits beside the int64 indices
+    mine = torch.stack([vals.to(torch.float32).contiguous().view(torch.int32).to(torch.int64),
+                        idx.to(torch.int64)], 0)
+    both = torch.empty(W, 2, B, k, dtype=torch.int64, device=mine.device)
+    if path == "rccl":
+        dist.all_gather_into_tensor(both, mine, group=table.group)
+    else:  # gloo (CPU tests): list form
+        dist.all_gather(list(both.unbind(0)), mine, group=table.group)
+    gv = both[:, 0].to(torch.int32).view(torch.float32)
+    return merge_fn(gv.transpose(0, 1).contiguous(), both[:, 1].transpose(0, 1).contiguous(), k)
+
+
 class PipelinedScorer:
     """Scores a stream of batches, each against its own all-gather of the table, with
     the gather of batch k+1 overlapped with the scoring of batch k (two gathered
