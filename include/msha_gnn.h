@@ -904,6 +904,74 @@ MSHA_API int msha_topk_merge(int64_t rows, int64_t lists, int64_t len, int32_t k
                              float* out_val, int64_t* out_idx, void* ws, size_t ws_bytes,
                              msha_stream_t stream);
 
+/* ---- Link-prediction training for the inner-product scorer (LLP.py:112-115 under a
+ * binary cross-entropy on the logit) (ABI 16, added) ------------------------------------
+ * sample -> score -> loss -> table gradient.  No entry point reads anything back to the
+ * host or allocates, so the whole chain can be captured into one HIP graph; no (P, F)
+ * array exists anywhere in it and no float atomic is used: every sum has a fixed order.
+ *
+ * Negative sampler.  For positive p in [0, n_pos) and j < k: src_rep[p k + j] = src[p] and
+ * dst_neg[p k + j] = d + col_offset, d drawn uniformly from the candidates [0, n_cand) that
+ * are not neighbours of src[p] in the CSR (rowptr int32 (n_rows + 1), col int32 (n_edges),
+ * ascending within a row; a row with rowflag (nullable, one byte a row) set is a virtual
+ * full row and counts as having no edges).  There is no rejection loop: with cnt = n_cand -
+ * deg and r = (philox(seed, offset, p k + j) * cnt) >> 32, d is the r-th non-edge column,
+ * r + t for the smallest t in [0, deg] with col[t] - t > r (binary search, at most 32
+ * steps).  dst_neg is -1 when cnt <= 0 and when src[p] is outside [0, n_rows), which is
+ * decided before any load through it.  The draw's offset follows the dropout draws: the
+ * installed replay counter (msha_set_rng_counter) is added in its high word, so a captured
+ * graph draws fresh negatives on every replay. */
+MSHA_API int msha_negative_sample(int64_t n_pos, int32_t k, const int64_t* src, int64_t n_rows,
+                                  int64_t n_cand, int64_t n_edges, const int32_t* rowptr,
+                                  const int32_t* col, const uint8_t* rowflag, int64_t col_offset,
+                                  uint64_t seed, uint64_t offset, int64_t* src_rep,
+                                  int64_t* dst_neg, msha_stream_t stream);
+/* Incidence plan of a pair list over a table of n rows (ABI 16, added).  The 2 n_pairs
+ * endpoints are numbered e < n_pairs: the src end of pair e (row src[e], other end dst[e]);
+ * e >= n_pairs: the dst end of pair e - n_pairs.  rowptr int32 (n + 1), ent int32
+ * (2 n_pairs): row r's endpoint ids, ascending (a stable sort by row), at
+ * ent[rowptr[r], rowptr[r + 1]).  A pair with either index outside [0, n) is padding: it is
+ * in no row, and ent past rowptr[n] holds -1.  A self pair is twice in its row.  A pure
+ * function of (src, dst, n): integer work, ranked placement.  chunk_tab: int32,
+ * 2 * msha_pair_plan_chunk_slots(n_pairs) words, the backward's chunk table: rows of more
+ * than msha_pair_plan_chunk() endpoints are cut into chunks of that size; a static bound, no
+ * count is read back.  2 n_pairs < 2^31, n < 2^31 - 1.  ws: msha_pair_plan_workspace_size
+ * bytes, 16-byte aligned, contents irrelevant.  n_pairs = 0 gives the empty plan. */
+MSHA_API int32_t msha_pair_plan_chunk(void);                  /* host-only (ABI 16, added) */
+MSHA_API int64_t msha_pair_plan_chunk_slots(int64_t n_pairs); /* host-only (ABI 16, added) */
+MSHA_API size_t msha_pair_plan_workspace_size(int64_t n_pairs); /* (ABI 16, added) */
+MSHA_API int msha_pair_plan(int64_t n_pairs, int64_t n, const int64_t* src, const int64_t* dst,
+                            int32_t* rowptr, int32_t* ent, int32_t* chunk_tab, void* ws,
+                            size_t ws_bytes, msha_stream_t stream);
+/* Fused loss (ABI 16, added).  z[p] = sum_f h[src[p], f] h[dst[p], f] in fp32 (h: (n, feat)
+ * fp32 or bf16, row pitch ld elements, 16-byte aligned rows; feat as msha_pair_inner_fwd_ex:
+ * a power of two, 16 bytes to 64 lanes x 16 bytes of a row -- msha_link_bce_supported),
+ * l = max(z, 0) - z y + log1p(exp(-|z|)) with target y in [0, 1] (soft targets allowed),
+ * loss[0] = sum_p w_p l_p with weight w (nullable: 1 / n_pairs).  A pair with an index
+ * outside [0, n) is padding: z = NaN, nothing added, counted in n_pad[0].  The sum is
+ * ordered: blocks of 1024 pairs, each in a fixed order, then the partials in order.
+ * ws: msha_link_bce_fwd_workspace_size bytes, 16-byte aligned.  1 <= n_pairs < 2^30. */
+MSHA_API int msha_link_bce_supported(int32_t feat, int32_t dtype); /* host-only (ABI 16, added) */
+MSHA_API size_t msha_link_bce_fwd_workspace_size(int64_t n_pairs);  /* (ABI 16, added) */
+MSHA_API int msha_link_bce_fwd(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
+                               int64_t ld, int64_t n, const int64_t* src, const int64_t* dst,
+                               const float* target, const float* weight, float* z, float* loss,
+                               int32_t* n_pad, void* ws, size_t ws_bytes, msha_stream_t stream);
+/* Its table gradient (ABI 16, added): dH (n, feat) fp32, contiguous, for either table type,
+ * dH[r] = sum over row r's endpoints e in plan order of g_p h[other(e)], g_p = gloss[0] w_p
+ * (sigmoid(z_p) - y_p) with z the forward's output and gloss a DEVICE scalar.  Every row is
+ * written (zeros without endpoints): no memset is needed.  A row of at most one chunk is
+ * summed by one wave in plan order, a longer one through chunk partials added in chunk
+ * order: the result depends on the plan alone, never on the grid.  The plan must be the one
+ * of (src, dst, n).  ws: msha_link_bce_bwd_workspace_size bytes, 16-byte aligned. */
+MSHA_API size_t msha_link_bce_bwd_workspace_size(int64_t n_pairs, int32_t feat); /* (ABI 16, added) */
+MSHA_API int msha_link_bce_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
+                               int64_t ld, int64_t n, const int64_t* src, const int64_t* dst,
+                               const float* target, const float* weight, const float* z,
+                               const float* gloss, const int32_t* plan_rowptr,
+                               const int32_t* plan_ent, const int32_t* plan_chunk_tab, float* dH,
+                               void* ws, size_t ws_bytes, msha_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

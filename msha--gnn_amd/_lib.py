@@ -220,6 +220,19 @@ SIGNATURES = {
                                   I32, I32, P, P, P, P, SZ, P]),
     "msha_topk_merge_workspace_size": (SZ, [I64, I64, I64, I32]),
     "msha_topk_merge": (C.c_int, [I64, I64, I64, I32, P, P, I32, P, P, P, SZ, P]),
+    # link-prediction training (ABI 16, added)
+    "msha_negative_sample": (C.c_int, [I64, I32, P, I64, I64, I64, P, P, P, I64, U64, U64, P, P,
+                                       P]),
+    "msha_pair_plan_chunk": (I32, []),
+    "msha_pair_plan_chunk_slots": (I64, [I64]),
+    "msha_pair_plan_workspace_size": (SZ, [I64]),
+    "msha_pair_plan": (C.c_int, [I64, I64, P, P, P, P, P, P, SZ, P]),
+    "msha_link_bce_supported": (C.c_int, [I32, I32]),
+    "msha_link_bce_fwd_workspace_size": (SZ, [I64]),
+    "msha_link_bce_fwd": (C.c_int, [I64, I32, I32, P, I64, I64, P, P, P, P, P, P, P, P, SZ, P]),
+    "msha_link_bce_bwd_workspace_size": (SZ, [I64, I32]),
+    "msha_link_bce_bwd": (C.c_int, [I64, I32, I32, P, I64, I64, P, P, P, P, P, P, P, P, P, P, P,
+                                    SZ, P]),
 }
 
 _lib = None

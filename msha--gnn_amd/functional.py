@@ -1227,6 +1227,192 @@ def topk_merge(vals, idx=None, k=1, sigmoid=False):
     return out_v, out_i
 
 
+# ----------------------------------------------------- link-prediction training ---
+def _pair_lists(src, dst, what):
+    if src.dtype != torch.int64 or dst.dtype != torch.int64:
+        raise TypeError(f"{what}: src and dst must be int64 index tensors")
+    if src.dim() != 1 or dst.dim() != 1 or src.numel() != dst.numel():
+        raise ValueError(f"{what}: src and dst must be 1-D and of one length, got "
+                         f"{tuple(src.shape)} and {tuple(dst.shape)}")
+    if 2 * src.numel() >= 2 ** 31:
+        raise ValueError(f"{what}: 2 * P must be below 2^31, got P = {src.numel()}")
+
+
+class PairPlan:
+    """Incidence plan of a pair list over a table of ``n`` rows (``pair_plan``): ``rowptr``
+    int32 (n + 1) and ``ent`` int32 (2P), row r's endpoint ids in ascending order
+    (e < P: the src end of pair e, e >= P: the dst end of pair e - P; padding pairs in no
+    row, ``ent`` past ``rowptr[n]`` is -1), plus the backward's chunk table.  Valid for as
+    long as the pair list is unchanged."""
+
+    def __init__(self, n, n_pairs, rowptr, ent, chunk_tab):
+        self.n, self.n_pairs = int(n), int(n_pairs)
+        self.rowptr, self.ent, self.chunk_tab = rowptr, ent, chunk_tab
+
+
+def pair_plan(src, dst, n: int) -> PairPlan:
+    """The ``PairPlan`` of the pairs (src[p], dst[p]) over ``n`` table rows
+    (``msha_pair_plan``): a stable device radix sort of the 2P endpoints by row.  A pure
+    function of its arguments; nothing is read back, so the call can be captured."""
+    _pair_lists(src, dst, "pair_plan")
+    n = int(n)
+    if not 1 <= n < 2 ** 31 - 1:
+        raise ValueError(f"pair_plan: n must be in [1, 2^31 - 1), got {n}")
+    _lib.require_cuda(src, dst)
+    if src.device != dst.device:
+        raise ValueError("pair_plan: src and dst must be on one device")
+    src, dst = src.contiguous(), dst.contiguous()
+    P, dev = src.numel(), src.device
+    rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    ent = torch.empty(2 * P, dtype=torch.int32, device=dev)
+    slots = _lib.fn("msha_pair_plan_chunk_slots")(P)
+    tab = torch.empty(2 * slots, dtype=torch.int32, device=dev)
+    ws = _workspace(dev, _lib.fn("msha_pair_plan_workspace_size")(P))
+    _lib.call("msha_pair_plan", P, n, src.data_ptr() if P else None,
+              dst.data_ptr() if P else None, rowptr.data_ptr(), ent.data_ptr() if P else None,
+              tab.data_ptr(), ws.data_ptr(), ws.numel(), _stream(src))
+    return PairPlan(n, P, rowptr, ent, tab)
+
+
+def sample_negatives(graph, src, k: int = 1, n_cand: int | None = None, seed: int | None = None,
+                     offset: int = 0, col_offset: int = 0):
+    """``k`` non-edges per positive: ``(src_rep, dst_neg)``, int64 of length P * k, the pair
+    (src[p], d) at p * k + j with d drawn exactly uniformly from the columns [0, n_cand)
+    (default: the graph's) that are not neighbours of src[p] (``msha_negative_sample``: no
+    rejection loop, one Philox draw and a binary search per pair).  ``graph``: a ``Graph``
+    or ``(rowptr, col[, rowflag])`` int32 CSR tensors with columns ascending within a row; a
+    virtual full row counts as having no edges.  d is -1 for a row without non-edges and
+    for a ``src`` outside the CSR's rows; ``col_offset`` is added to d.  Draws follow
+    (``seed``, ``offset``) and the installed replay counter (``set_rng_counter``): a captured
+    graph draws fresh negatives on every replay."""
+    if isinstance(graph, Graph):
+        rowptr, col, rowflag, cols = graph.rowptr, graph.col, graph.rowflag, graph.n_cols
+    else:
+        rowptr, col = graph[0], graph[1]
+        rowflag = graph[2] if len(graph) > 2 else None
+        cols = None
+    if n_cand is None:
+        if cols is None:
+            raise ValueError("sample_negatives: n_cand is needed with a bare CSR")
+        n_cand = cols
+    n_cand, k = int(n_cand), int(k)
+    if k < 1:
+        raise ValueError(f"sample_negatives: k must be at least 1, got {k}")
+    if not 0 <= n_cand < 2 ** 31:
+        raise ValueError(f"sample_negatives: n_cand must be in [0, 2^31), got {n_cand}")
+    if src.dtype != torch.int64 or src.dim() != 1:
+        raise TypeError("sample_negatives: src must be a 1-D int64 tensor")
+    if rowptr.dtype != torch.int32 or col.dtype != torch.int32 or rowptr.numel() < 1:
+        raise TypeError("sample_negatives: the CSR is (rowptr, col) int32 tensors")
+    if rowflag is not None and (rowflag.dtype not in (torch.uint8, torch.bool)
+                                or rowflag.numel() != rowptr.numel() - 1):
+        raise TypeError("sample_negatives: rowflag is one uint8 per CSR row")
+    _lib.require_cuda(src, rowptr, col, rowflag)
+    src, rowptr, col = src.contiguous(), rowptr.contiguous(), col.contiguous()
+    if rowflag is not None:
+        rowflag = rowflag.contiguous()
+    if seed is None:
+        seed = new_seed()
+    P, dev = src.numel(), src.device
+    src_rep = torch.empty(P * k, dtype=torch.int64, device=dev)
+    dst_neg = torch.empty(P * k, dtype=torch.int64, device=dev)
+    _lib.call("msha_negative_sample", P, k, src.data_ptr() if P else None, rowptr.numel() - 1,
+              n_cand, col.numel(), rowptr.data_ptr(), col.data_ptr() if col.numel() else None,
+              _lib.ptr(rowflag), int(col_offset), int(seed), int(offset), src_rep.data_ptr(),
+              dst_neg.data_ptr(), _stream(src))
+    return src_rep, dst_neg
+
+
+class _LinkBCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, src, dst, target, weight, plan):
+        dt = h.dtype
+        hh = h.detach()
+        esz = hh.element_size()
+        if not (hh.stride(1) == 1 and (hh.stride(0) * esz) % 16 == 0 and hh.data_ptr() % 16 == 0):
+            hh = hh.contiguous()
+        n, Fd = hh.shape
+        P, dev, s = src.numel(), hh.device, _stream(hh)
+        z = torch.empty(P, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        npad = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = _workspace(dev, _lib.fn("msha_link_bce_fwd_workspace_size")(P))
+        _lib.call("msha_link_bce_fwd", P, Fd, _code(dt), hh.data_ptr(), hh.stride(0), n,
+                  src.data_ptr(), dst.data_ptr(), target.data_ptr(), _lib.ptr(weight),
+                  z.data_ptr(), loss.data_ptr(), npad.data_ptr(), ws.data_ptr(), ws.numel(), s)
+        ctx.plan, ctx.dt = plan, dt
+        ctx.save_for_backward(hh, src, dst, target, weight, z)
+        ctx.mark_non_differentiable(z, npad)
+        return loss, z, npad
+
+    @staticmethod
+    def backward(ctx, gloss, _gz=None, _gpad=None):
+        hh, src, dst, target, weight, z = ctx.saved_tensors
+        n, Fd = hh.shape
+        P, dev = src.numel(), hh.device
+        plan = ctx.plan
+        g = gloss.detach().to(torch.float32).reshape(1).contiguous()
+        dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
+        ws = _workspace(dev, _lib.fn("msha_link_bce_bwd_workspace_size")(P, Fd))
+        _lib.call("msha_link_bce_bwd", P, Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n,
+                  src.data_ptr(), dst.data_ptr(), target.data_ptr(), _lib.ptr(weight),
+                  z.data_ptr(), g.data_ptr(), plan.rowptr.data_ptr(), plan.ent.data_ptr(),
+                  plan.chunk_tab.data_ptr(), dH.data_ptr(), ws.data_ptr(), ws.numel(),
+                  _stream(hh))
+        return (dH if ctx.dt == torch.float32 else dH.to(ctx.dt)), None, None, None, None, None
+
+
+def link_bce_loss(h, src, dst, target, weight=None, plan=None, return_logits=False):
+    """Binary cross-entropy of the inner-product link logits, fused with the caller's gather
+    and with a deterministic table gradient:
+
+        F.binary_cross_entropy_with_logits((h[src] * h[dst]).sum(-1), target, weight,
+                                           reduction="sum")
+
+    and, with ``weight=None``, the mean.  ``h`` (n, F) float32 or bfloat16 (F a power of two
+    spanning 16 bytes to 64 lanes x 16 bytes of a row); ``src`` / ``dst`` int64 (P,);
+    ``target`` (P,) in [0, 1], soft targets allowed; ``weight`` (P,) or None.  A pair with an
+    index outside [0, n) is padding: it adds nothing (``return_logits`` shows NaN for it).
+    Returns the fp32 scalar loss, or ``(loss, logits)`` with ``return_logits``.
+
+    The gradient goes to ``h`` only (a bf16 ``h`` receives it cast from the fp32 sum).  It is
+    summed per table row in the order of ``plan`` (``pair_plan(src, dst, n)``, built here
+    when None; reuse it for as long as the pair list is unchanged) with no float atomics:
+    bitwise reproducible.  Nothing (P, F)-sized is materialised and nothing is read back, so
+    plan + loss + backward can be captured into one HIP graph."""
+    if h.dtype not in (torch.float32, BF16):
+        raise TypeError(f"link_bce_loss takes a float32 or bfloat16 table, got {h.dtype}")
+    if h.dim() != 2:
+        raise ValueError(f"link_bce_loss: h must be (n, F), got {tuple(h.shape)}")
+    _pair_lists(src, dst, "link_bce_loss")
+    P = src.numel()
+    if P < 1 or h.shape[0] < 1:
+        raise ValueError("link_bce_loss: needs at least one pair and one table row")
+    if not target.is_floating_point() or target.shape != (P,):
+        raise ValueError(f"link_bce_loss: target must be a float tensor of shape ({P},), got "
+                         f"{target.dtype} {tuple(target.shape)}")
+    if weight is not None and (not weight.is_floating_point() or weight.shape != (P,)):
+        raise ValueError(f"link_bce_loss: weight must be a float tensor of shape ({P},), got "
+                         f"{weight.dtype} {tuple(weight.shape)}")
+    if plan is not None and (not isinstance(plan, PairPlan) or plan.n != h.shape[0]
+                             or plan.n_pairs != P):
+        raise ValueError("link_bce_loss: plan is not a PairPlan of this pair list and table")
+    if not _lib.fn("msha_link_bce_supported")(h.shape[1], _code(h.dtype)):
+        raise ValueError(f"link_bce_loss: feature width {h.shape[1]} of a {h.dtype} table is "
+                         f"not supported (a power of two, 16 bytes to 64 lanes x 16 bytes)")
+    for t in (src, dst, target, weight):
+        if t is not None and t.device != h.device:
+            raise ValueError("link_bce_loss: every tensor must be on the table's device")
+    _lib.require_cuda(h)
+    target = target.detach().to(torch.float32).contiguous()
+    weight = weight.detach().to(torch.float32).contiguous() if weight is not None else None
+    src, dst = src.contiguous(), dst.contiguous()
+    if plan is None and h.requires_grad and torch.is_grad_enabled():
+        plan = pair_plan(src, dst, h.shape[0])  # only a backward reads it
+    loss, z, _ = _LinkBCE.apply(h, src, dst, target, weight, plan)
+    return (loss, z) if return_logits else loss
+
+
 # --------------------------------------------------------- full MSHA layer (Ours) ---
 # the bipartite kernels' block-partial reduce rides in the Ours layer's prep / finish
 # launches (msha_bip_defer_reduce; one graph node fewer each way); MSHA_BIP_DEFER=0: separate

@@ -337,6 +337,18 @@ class LinkPredictor(torch.nn.Module):
         return MF.topk_inner(h, h if candidates is None else candidates, k, rows=src,
                              exclude=exclude, sigmoid=True)
 
+    def loss(self, h, src, dst, target, weight=None, plan=None):
+        """Binary cross-entropy of this predictor's link logits against ``target``, with
+        the caller's gather fused and a deterministic gradient to ``h``
+        (``functional.link_bce_loss``: the sum over pairs under ``weight``, the mean
+        without).  'inner' only: the reference's 'mlp' head returns a (B, hidden) vector per
+        pair (LLP.py:107-111), which gives no scalar logit to take the loss of."""
+        if self.predictor != "inner":
+            raise ValueError(f"LinkPredictor.loss needs the 'inner' predictor: "
+                             f"{self.predictor!r} scores a pair with a vector (LLP.py:107-115), "
+                             f"so there is no scalar to rank by")
+        return MF.link_bce_loss(h, src, dst, target, weight=weight, plan=plan)
+
 
 class OursLayer(OursLayer3):
     """Ours.py:29-109: OursLayer3's inter attention plus the intra-source attention
