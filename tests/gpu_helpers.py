@@ -53,10 +53,11 @@ BF16_STORE = 2.0 ** -9  # one round-to-nearest bf16 storage rounding, relative
 BF16_SPLIT2 = 2.0 ** -18
 
 
-def bounded_close(got, ref, absterms, nterms, rtol, name="", u=U32, store_u=0.0, split_u=0.0):
+def bounded_close(got, ref, absterms, nterms, rtol, name="", u=U32, store_u=0.0, split_u=0.0,
+                  floor=0.0):
     """Sums against an fp64 reference, EVERY element (no fraction clause):
 
-        |got - ref| <= rtol |ref| + store_u |ref| + 4 sqrt(n) u A
+        |got - ref| <= rtol |ref| + store_u |ref| + 4 sqrt(n) u A  (+ split_u A + floor)
 
     A = the sum of the absolute values of the terms (incl. the magnitudes inside each
     term, e.g. |g| + |D| of a score gradient), n = the number of terms plus the ops
@@ -69,7 +70,9 @@ def bounded_close(got, ref, absterms, nterms, rtol, name="", u=U32, store_u=0.0,
     exact bf16 values, fed to the reference as such, and they accumulate in fp32);
     ``store_u``: the result's own storage rounding (a bf16 output: 2^-9, BF16_STORE);
     ``split_u``: a deterministic per-term operand error, bound + split_u A (an fp32 operand
-    carried as two bf16 terms on the matrix cores: 2^-18, BF16_SPLIT2).
+    carried as two bf16 terms on the matrix cores: 2^-18, BF16_SPLIT2; a softmax weight
+    whose exp argument is large: ``cond_split_u``); ``floor``: an absolute term (terms that
+    underflow to 0 in fp32: COND_FLOOR).
     Returns (max err / bound, fraction within rtol |ref| alone) for reporting."""
     got = np.asarray(got, np.float64)
     ref = np.asarray(ref, np.float64)
@@ -79,7 +82,8 @@ def bounded_close(got, ref, absterms, nterms, rtol, name="", u=U32, store_u=0.0,
         n = n.reshape((-1,) + (1,) * (ref.ndim - 1))
     n = np.broadcast_to(n, ref.shape)
     err = np.abs(got - ref)
-    bound = (rtol + store_u) * np.abs(ref) + (STAT_C * np.sqrt(n) * u + split_u) * A + 1e-300
+    bound = ((rtol + store_u) * np.abs(ref) + (STAT_C * np.sqrt(n) * u + split_u) * A + floor
+             + 1e-300)
     worst = float((err / bound).max()) if err.size else 0.0
     assert np.all(err <= bound), (
         f"{name}: {int((err > bound).sum())} of {err.size} elements beyond "
@@ -164,9 +168,14 @@ def rms_close(got, ref, rtol, name=""):
 
 def _seg_sum(x, ptr):
     """Sums of x over the contiguous segments [ptr[k], ptr[k+1]) of axis 0 (empty ones 0),
-    via a running sum (the terms here are non-negative)."""
-    cs = np.concatenate([np.zeros((1,) + x.shape[1:]), np.cumsum(x, axis=0)])
-    return cs[ptr[1:]] - cs[ptr[:-1]]
+    each segment summed on its own: a difference of running sums would lose a segment of
+    tiny terms (underflowing softmax weights) against the total before it."""
+    ptr = np.asarray(ptr, np.int64)
+    out = np.zeros((len(ptr) - 1,) + x.shape[1:])
+    nz = np.flatnonzero(ptr[1:] > ptr[:-1])
+    if len(nz):
+        out[nz] = np.add.reduceat(x[:ptr[-1]], ptr[nz], axis=0)
+    return out
 
 
 def edge_abs_terms(rowptr, col, fwd, hc, dU, hs=None, dV=None, keep=None, p=0.0, slope=0.2):
@@ -219,3 +228,114 @@ def edge_abs_terms(rowptr, col, fwd, hc, dU, hs=None, dV=None, keep=None, p=0.0,
     out["n_row"] = np.diff(rowptr).astype(np.float64) + k_in
     out["n_col"] = nnz.astype(np.float64) + k_in
     return out
+
+
+# ---------------------------------------------------------------- ill-conditioned scores
+COND_C = 8.0  # roundings of a softmax weight's exp argument allowed for (cond_split_u)
+COND_FLOOR = 2.0 ** -100
+REGIMES = ("shift_up", "shift_down", "ramp_up", "ramp_down", "dominant", "kink")
+
+# (n, m, H, F, max_deg, extra): the smallest graphs that reach every path of the
+# edge-softmax family -- G*: the general kernels (rows longer than one wavefront, several
+# online chunks; a hot column; QPL > 1), S*: short rows (gather layout), B*: bipartite
+COND_CASES = {
+    "G1": (150, 80, 1, 8, 80, dict(empty_rows=(0,), full_rows=(2,))),
+    "G2": (400, 400, 8, 16, 70, dict(hot_col=9)),
+    "G3": (64, 40, 8, 128, 12, dict(empty_rows=(1,))),
+    "S1": (400, 32, 2, 64, 12, dict()),
+    "S2": (300, 40, 8, 16, 5, dict(empty_rows=(0,))),
+    "B1": (700, 32, 2, 64, 32, dict(full_rows=(1, 2, 3, 40), empty_rows=(5,))),
+    "B2": (900, 8, 8, 16, 5, dict(empty_rows=(0,))),
+}
+
+
+def score_regimes(rng, n, m, H):
+    """Named (el, er) pairs in float32, each from a standard_normal base, that leave the
+    few-units-around-0 range every other parity test draws its scores from:
+
+    shift_up    el += 96: exp overflows without the max subtraction (96 > 88.7)
+    shift_down  el -= 600: scores near -120 after the 0.2 slope; l underflows to 0 without
+                the max subtraction, lse is large and negative
+    ramp_up     er[j] += 3 j: CSR columns ascend, so every chunk of a long row raises the
+                running max (the rescale of acc, l, lc, uc, qc; alpha underflowing to 0)
+    ramp_down   er[j] -= 3 j: later chunks whose weights underflow (alpha == 1, psum == 0)
+    dominant    er[5] += 200 on every head: att is exactly 1 on one edge and 0 on the rest
+                of the row (ds == 0, no NaN from 0 * inf)
+    kink        el, er = rint(base): pre == 0 exactly on many edges (the forward branch and
+                lrelu'(0) = slope, the oracle's pre > 0)"""
+    el = rng.standard_normal((n, H)).astype(np.float32)
+    er = rng.standard_normal((m, H)).astype(np.float32)
+    ramp = (3.0 * np.arange(m, dtype=np.float32))[:, None]
+    dom = er.copy()
+    dom[5] += np.float32(200)
+    return {
+        "shift_up": (el + np.float32(96), er.copy()),
+        "shift_down": (el - np.float32(600), er.copy()),
+        "ramp_up": (el.copy(), er + ramp),
+        "ramp_down": (el.copy(), er - ramp),
+        "dominant": (el.copy(), dom),
+        "kink": (np.rint(el), np.rint(er)),
+    }
+
+
+def score_span(rowptr, col, el, er):
+    """S of ``cond_split_u``: the largest |el_i + er_j| over the edges plus ln(max degree)
+    (|s| <= |pre|, and |lse| <= max |s| + ln(deg))."""
+    rowptr = np.asarray(rowptr, np.int64)
+    rows = np.repeat(np.arange(len(rowptr) - 1), np.diff(rowptr))
+    pre = np.asarray(el, np.float64)[rows] + np.asarray(er, np.float64)[np.asarray(col, np.int64)]
+    return float(np.abs(pre).max() + np.log(np.diff(rowptr).max()))
+
+
+def cond_split_u(S):
+    """``split_u`` of ``bounded_close`` for softmax weights at scores of magnitude up to S:
+    COND_C 2^-24 S.  A weight exp(s - lse) inherits, as a relative error, the absolute error
+    of its argument: one rounding each of el + er, of the slope multiply, of m + log(l) in
+    the forward, of the stored lse, of lse * log2e (or m2) and of the difference (none where
+    it is an fma) -- six roundings of at most 2^-24 max(|s|, |lse|) <= 2^-24 S, and two
+    spare."""
+    return COND_C * U32 * S
+
+
+def cond_inputs(key, seed=0):
+    """One COND_CASES graph with its tables and every score regime (float32), from a fixed
+    seed: dict(c, rowptr, col, empty, hc, hs, dU, dV, regimes, shape)."""
+    n, m, H, F, max_deg, kw = COND_CASES[key]
+    rng = np.random.default_rng(1000 + seed + n + 7 * H + F)
+    c = random_counts(rng, n, m, max_deg, **kw)
+    rowptr, col, empty = virtual_csr(c)
+    tab = lambda *s: rng.standard_normal(s).astype(np.float32)  # noqa: E731
+    hc, hs, dU, dV = tab(m, H, F), tab(n, H, F), tab(n, H, F), tab(m, H, F)
+    return dict(c=c, rowptr=rowptr, col=col, empty=empty, hc=hc, hs=hs, dU=dU, dV=dV,
+                regimes=score_regimes(rng, n, m, H), shape=(n, m, H, F))
+
+
+COND_NAMES = ("u", "v", "d_el", "d_er", "d_hc", "d_hs")
+_COND_PER = {"u": "n_row", "d_hs": "n_row", "d_el": "n_row", "v": "n_col", "d_hc": "n_col",
+             "d_er": "n_col"}
+
+
+def cond_reference(rowptr, col, empty, el, er, hc, dU, hs=None, dV=None, keep=None, p=0.0):
+    """The fp64 oracle (forward and backward) on the given stored values, with the absolute
+    terms and the score span: (refs by COND_NAMES, A of edge_abs_terms, S, forward dict)."""
+    d = lambda x: None if x is None else np.asarray(x, np.float64)  # noqa: E731
+    fwd = O.edge_aggregate_fwd(rowptr, col, d(el), d(er), d(hc), hs=d(hs), keep=keep, p=p,
+                               rowflag=empty)
+    bw = O.edge_aggregate_bwd(rowptr, col, fwd, d(hc), d(dU), hs=d(hs), dV=d(dV), keep=keep, p=p)
+    A = edge_abs_terms(rowptr, col, fwd, d(hc), d(dU), hs=d(hs), dV=d(dV), keep=keep, p=p)
+    refs = dict(u=fwd["u"], v=fwd["v"], d_el=bw["d_el"], d_er=bw["d_er"], d_hc=bw["d_hc"],
+                d_hs=bw["d_hs"])
+    return refs, A, score_span(rowptr, col, el, er), fwd
+
+
+def cond_close(got, refs, A, S, rtol, tag=""):
+    """``bounded_close`` of every output in ``got`` (name -> array) at the ill-conditioned
+    bound: rtol |ref| + (4 sqrt(n) 2^-24 + cond_split_u(S)) A + COND_FLOOR (a weight below
+    2^-126 of its row's largest is 0 in fp32; with |values| <= 2^4 and at most 2^13 terms
+    nothing lost that way reaches 2^-100).  Returns the worst error-to-bound ratio."""
+    worst = 0.0
+    for name, x in got.items():
+        w, _ = bounded_close(x, refs[name], A[name], A[_COND_PER[name]], rtol, f"{tag} {name}",
+                             split_u=cond_split_u(S), floor=COND_FLOOR)
+        worst = max(worst, w)
+    return worst

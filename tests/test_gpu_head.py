@@ -89,14 +89,16 @@ def _reference(u, v, bns, W, mask, keep_x, keep_g, p, training, dout):
     return out.detach(), grads, runs
 
 
-def _run(cuda, n, m, H, F_, p, training, dtype=torch.float32, sparse=True, seed=0):
+def _run(cuda, n, m, H, F_, p, training, dtype=torch.float32, sparse=True, seed=0, w_scale=1.0):
+    """``w_scale`` multiplies W (tests/test_gpu_conditioning.py: logits in the hundreds, or
+    elu / expm1 near 0)."""
     from msha_gnn_amd import functional as MF
 
     g, mask = _graph(n, m, seed, cuda)
     gen = torch.Generator().manual_seed(seed + 1)
     u = (torch.randn(n, H, F_, generator=gen)).to(cuda, dtype)
     v = (torch.randn(m, H, F_, generator=gen)).to(cuda, dtype)
-    W = (torch.randn(H * m, m, generator=gen) * (H * m) ** -0.5).to(cuda)
+    W = (torch.randn(H * m, m, generator=gen) * (H * m) ** -0.5).to(cuda) * w_scale
     a = torch.zeros(2 * m, 1, device=cuda)
     bns = _bns(H, F_, cuda, seed + 2)
     for pair in bns:
