@@ -904,6 +904,63 @@ MSHA_API int msha_topk_merge(int64_t rows, int64_t lists, int64_t len, int32_t k
                              float* out_val, int64_t* out_idx, void* ws, size_t ws_bytes,
                              msha_stream_t stream);
 
+/* ---- Filtered link ranks, MRR and Hits@K for the inner-product scorer (LLP.py:20, the
+ * ranking protocol around it) (ABI 16, added) ------------------------------------------
+ * For query position b in [0, n_q) with target candidate t = target[b] (a GLOBAL row; it
+ * is local when col_offset <= t < col_offset + n_cand):
+ *   greater[b] = #{ j in [0, n_cand), j != t, j not excluded for b : z_bj >  z_bt }
+ *   equal[b]   = the same set with ==
+ * z_bj = sum_f Q[q, f] * T[j, f], q = qi[b] (qi NULL: b): msha_topk_inner's logits, bit for
+ * bit (the same MFMA chain ordered by f alone), compared under its order: -0.0 folded onto
+ * +0.0, +inf highest, every NaN below -inf and all NaNs equal among themselves.  The target's
+ * own logit comes from the same chain (its row is staged as one more candidate), so a
+ * candidate row bytewise equal to the target row ties with it exactly; out_logit[b]
+ * (nullable) is that logit, the value msha_topk_inner(sigmoid = 0) reports for the pair.
+ * The (n_q, n_cand) score matrix is never written; one pass serves every K:
+ * rank = 1 + greater + {0, equal / 2, equal}.
+ *
+ * target_logit_in (nullable, fp32 n_q): the logit to rank against instead (the sharded
+ * case: the target's owner computed it); then a target that is not local is allowed and
+ * every non-excluded candidate is counted; a local target is still left out of the counts.
+ * Without it a target that is not local gives greater = equal = -1 for the row and sets
+ * bit 2 of *err (nullable).  A qi[b] outside [0, rows_q) gives -1 / -1 and sets bit 1;
+ * nothing is read through it.  out_logit of such rows is NaN.
+ *
+ * excl_rowptr / excl_col, splits, Q / T alignment and pitches: as msha_topk_inner.  Each
+ * column split writes partial counts into ws and a finishing launch sums them: integer adds
+ * only, so the result does not depend on splits, bit for bit.  ws:
+ * msha_rank_inner_workspace_size bytes, 16-byte aligned, contents irrelevant.  feat a
+ * multiple of 16 in [16, 256], n_cand < 2^31 - 1; n_q = 0 launches nothing; n_cand = 0 with
+ * target_logit_in returns zeros.  Stateless; ordinary stores, no float atomics. */
+/* host-only (ABI 16, added) */
+MSHA_API int msha_rank_inner_supported(int32_t feat, int32_t dtype);
+/* host-only: the default split count -- one (fp32) or two (bf16) blocks per CU from query
+ * tiles (128 rows) x splits, at least 512 candidates per split (ABI 16, added) */
+MSHA_API int msha_rank_inner_splits(int64_t n_q, int64_t n_cand, int32_t feat, int32_t dtype);
+/* bytes of ws for msha_rank_inner; splits 0: enough for either dtype's default split count
+ * (ABI 16, added) */
+MSHA_API size_t msha_rank_inner_workspace_size(int64_t n_q, int64_t n_cand, int32_t splits);
+/* the ranking itself, as described above (ABI 16, added) */
+MSHA_API int msha_rank_inner(int64_t n_q, int32_t feat, int32_t dtype, const void* Q,
+                             int64_t ldq, const int64_t* qi, int64_t rows_q, const void* T,
+                             int64_t ldt, int64_t n_cand, int64_t col_offset,
+                             const int64_t* target, const float* target_logit_in,
+                             const int32_t* excl_rowptr, const int32_t* excl_col,
+                             int32_t splits, int64_t* out_greater, int64_t* out_equal,
+                             float* out_logit, int32_t* err, void* ws, size_t ws_bytes,
+                             msha_stream_t stream);
+/* Sums over n ranked rows (ABI 16, added).  rank = 1 + greater + {0, equal / 2, equal} for
+ * ties = 0 (optimistic), 1 (mean), 2 (pessimistic), carried as the integer 2 rank; rows with
+ * greater < 0 are left out.  ks: nk <= 8 values of k >= 1 in HOST memory, read during the
+ * call.  out_counts (device, int64, nk + 2): the rows with 2 rank <= 2 ks[i], the valid
+ * rows, the sum of 2 rank.  out_rr (device, fp64): the sum of 1 / rank, in a fixed order
+ * (lanes stride a block's rows, xor tree, waves in order, blocks in order): two calls give
+ * the same bits.  ws: msha_rank_summary_workspace_size bytes, 16-byte aligned. */
+MSHA_API size_t msha_rank_summary_workspace_size(int64_t n); /* (ABI 16, added) */
+MSHA_API int msha_rank_summary(int64_t n, const int64_t* greater, const int64_t* equal,
+                               int32_t ties, const int64_t* ks, int32_t nk, int64_t* out_counts,
+                               double* out_rr, void* ws, size_t ws_bytes, msha_stream_t stream);
+
 /* ---- Link-prediction training for the inner-product scorer (LLP.py:112-115 under a
  * binary cross-entropy on the logit) (ABI 16, added) ------------------------------------
  * sample -> score -> loss -> table gradient.  No entry point reads anything back to the

@@ -220,6 +220,14 @@ SIGNATURES = {
                                   I32, I32, P, P, P, P, SZ, P]),
     "msha_topk_merge_workspace_size": (SZ, [I64, I64, I64, I32]),
     "msha_topk_merge": (C.c_int, [I64, I64, I64, I32, P, P, I32, P, P, P, SZ, P]),
+    # filtered link ranks (ABI 16, added)
+    "msha_rank_inner_supported": (C.c_int, [I32, I32]),
+    "msha_rank_inner_splits": (C.c_int, [I64, I64, I32, I32]),
+    "msha_rank_inner_workspace_size": (SZ, [I64, I64, I32]),
+    "msha_rank_inner": (C.c_int, [I64, I32, I32, P, I64, P, I64, P, I64, I64, I64, P, P, P, P,
+                                  I32, P, P, P, P, P, SZ, P]),
+    "msha_rank_summary_workspace_size": (SZ, [I64]),
+    "msha_rank_summary": (C.c_int, [I64, P, P, I32, P, I32, P, P, P, SZ, P]),
     # link-prediction training (ABI 16, added)
     "msha_negative_sample": (C.c_int, [I64, I32, P, I64, I64, I64, P, P, P, I64, U64, U64, P, P,
                                        P]),

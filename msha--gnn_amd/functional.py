@@ -1227,6 +1227,98 @@ def topk_merge(vals, idx=None, k=1, sigmoid=False):
     return out_v, out_i
 
 
+# ------------------------------------------------------------ filtered link ranks ---
+def rank_inner(q, table, target, rows=None, exclude=None, col_offset=0, target_logit=None,
+               splits=None, check=True):
+    """The filtered rank counts of each query's target among the rows of ``table``, without
+    the (B, n) score matrix: ``(greater, equal, logit)``, int64, int64 and float32, (B,)
+    each.  Query b is ``q[rows[b]]`` (``rows`` None: ``q[b]``), its target the row
+    ``target[b] - col_offset`` of ``table``; ``greater[b]`` / ``equal[b]`` count the other,
+    non-excluded candidates whose logit is above / equal to the target's ``logit[b]`` --
+    the logits and the order of ``topk_inner(..., sigmoid=False)``, bit for bit (NaN below
+    -inf, -0.0 == +0.0), so rank = 1 + greater + {0, equal / 2, equal}
+    (``metrics.rank_metrics``).  Dtypes, alignment, ``rows``, ``exclude`` and ``splits`` as
+    ``topk_inner``; the result does not depend on ``splits``.
+
+    ``target_logit`` (float32, (B,)): rank against these logits instead (a shard of a larger
+    table: ``col_offset`` is the shard's first global row and the target's owner computed
+    the logit); a target outside the shard is then allowed and every non-excluded row is
+    counted.
+
+    ``check`` (default) applies torch's index rule to ``rows`` and, without
+    ``target_logit``, to ``target`` against the table's rows (IndexError outside [-n, n),
+    negatives wrapped; one stream sync).  With ``check=False`` no host sync happens (the
+    call can be captured into a HIP graph); a stray ``rows[b]`` or a target outside the
+    table gives -1 / -1 (and a NaN logit) for that row only.  Inference only: the outputs
+    are detached."""
+    if q.dtype != table.dtype:
+        raise TypeError(f"q and table must share a dtype, got {q.dtype} and {table.dtype}")
+    if q.dtype not in (torch.float32, BF16):
+        raise TypeError("rank_inner takes float32 or bfloat16 tables")
+    if q.dim() != 2 or table.dim() != 2 or q.shape[1] != table.shape[1]:
+        raise ValueError(f"q and table must be 2-D with one feature width, got "
+                         f"{tuple(q.shape)} and {tuple(table.shape)}")
+    Fd = q.shape[1]
+    code = _code(q.dtype)
+    _lib.require_cuda(q, table, rows, target, target_logit)
+    if not _lib.fn("msha_rank_inner_supported")(Fd, code):
+        raise ValueError(f"rank_inner: feature width {Fd} must be a multiple of 16 in [16, 256]")
+    B = rows.numel() if rows is not None else q.shape[0]
+    if target.dim() != 1 or target.numel() != B or target.dtype != torch.int64:
+        raise ValueError(f"target must be an int64 vector with one entry per query ({B})")
+    if target_logit is not None and (target_logit.dtype != torch.float32
+                                     or target_logit.dim() != 1 or target_logit.numel() != B):
+        raise ValueError(f"target_logit must be a float32 vector with one entry per query ({B})")
+    q, table = q.detach(), table.detach()
+    esz = q.element_size()
+
+    def aligned(t):
+        return (t.stride(1) == 1 and (t.stride(0) * esz) % 16 == 0 and t.stride(0) >= Fd
+                and t.data_ptr() % 16 == 0)
+
+    if not aligned(q):
+        q = q.contiguous()
+    if not aligned(table):
+        table = table.contiguous()
+    dev = q.device
+    n = table.shape[0]
+    col_offset = int(col_offset)
+    if check and B:
+        if rows is not None:
+            rows, _ = check_pair_indices(rows, rows, q.shape[0])
+        if target_logit is None:
+            local, _ = check_pair_indices(target - col_offset if col_offset else target,
+                                          target, n, 1 << 62)
+            target = local + col_offset if col_offset else local
+    if rows is not None:
+        rows = rows.to(torch.int64).contiguous()
+    target = target.contiguous()
+    if target_logit is not None:
+        target_logit = target_logit.detach().contiguous()
+    rp = cp = None
+    if exclude is not None:
+        rp, cp = exclude
+        _lib.require_cuda(rp, cp)
+        if rp.dtype != torch.int32 or cp.dtype != torch.int32 or rp.numel() != B + 1:
+            raise ValueError("exclude must be (rowptr, col) int32 tensors with B + 1 row "
+                             "pointers (exclude_from_pairs)")
+        rp, cp = rp.contiguous(), cp.contiguous()
+        if cp.numel() == 0:  # a NULL column list would read as "no exclusion half given"
+            rp = cp = None
+    splits = 0 if splits is None else int(splits)
+    greater = torch.empty(B, dtype=torch.int64, device=dev)
+    equal = torch.empty(B, dtype=torch.int64, device=dev)
+    logit = torch.empty(B, dtype=torch.float32, device=dev)
+    need = _lib.fn("msha_rank_inner_workspace_size")(B, n, splits)
+    ws = _workspace(dev, need)
+    _lib.call("msha_rank_inner", B, Fd, code, q.data_ptr(), q.stride(0), _lib.ptr(rows),
+              q.shape[0], table.data_ptr() if n else None, table.stride(0), n, col_offset,
+              target.data_ptr(), _lib.ptr(target_logit), _lib.ptr(rp), _lib.ptr(cp), splits,
+              greater.data_ptr(), equal.data_ptr(), logit.data_ptr(), None, ws.data_ptr(),
+              ws.numel(), _stream(q))
+    return greater, equal, logit
+
+
 # ----------------------------------------------------- link-prediction training ---
 def _pair_lists(src, dst, what):
     if src.dtype != torch.int64 or dst.dtype != torch.int64:

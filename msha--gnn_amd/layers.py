@@ -337,6 +337,21 @@ class LinkPredictor(torch.nn.Module):
         return MF.topk_inner(h, h if candidates is None else candidates, k, rows=src,
                              exclude=exclude, sigmoid=True)
 
+    def rank(self, h, src, dst, candidates=None, exclude=None):
+        """The filtered rank counts of each true endpoint ``dst[b]`` (a row of
+        ``candidates``, default ``h`` itself) for the query ``h[src[b]]`` among all rows of
+        ``candidates``: ``(greater, equal, logit)`` (``functional.rank_inner``; feed the
+        counts to ``metrics.rank_metrics`` for MRR, mean rank and Hits@K).  ``exclude``:
+        the known edges (``functional.exclude_from_pairs``).  'inner' only: the reference's
+        'mlp' head returns a (B, hidden) vector per pair (LLP.py:107-111), which gives no
+        scalar to rank by."""
+        if self.predictor != "inner":
+            raise ValueError(f"LinkPredictor.rank needs the 'inner' predictor: "
+                             f"{self.predictor!r} scores a pair with a vector (LLP.py:107-115), "
+                             f"so there is no scalar to rank by")
+        return MF.rank_inner(h, h if candidates is None else candidates, dst, rows=src,
+                             exclude=exclude)
+
     def loss(self, h, src, dst, target, weight=None, plan=None):
         """Binary cross-entropy of this predictor's link logits against ``target``, with
         the caller's gather fused and a deterministic gradient to ``h``

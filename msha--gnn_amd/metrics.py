@@ -273,3 +273,65 @@ def hits_at_k(pos, neg, k):
         hits = (p > kth).sum()
     hits, bad = torch.stack([hits, bad.to(torch.int64)]).tolist()
     return float("nan") if bad else hits / p.numel()
+
+
+RANK_TIES = {"optimistic": 0, "mean": 1, "pessimistic": 2}
+
+
+def rank_metrics(greater, equal, ks=(1, 3, 10), ties="mean"):
+    """MRR, mean rank and Hits@K of filtered link ranks from the counts of
+    ``functional.rank_inner``: rank = 1 + greater + {0, equal / 2, equal} for ``ties`` =
+    'optimistic', 'mean' or 'pessimistic'.  Rows with ``greater < 0`` (no rank) are left
+    out.  One ``msha_rank_summary`` call and one readback: the hit counts and the rank sum
+    are integers (2 * rank, so the mean-tie half is exact), the reciprocal-rank sum is fp64
+    in a fixed order -- two calls give the same bits.  Returns ``{"mrr", "mean_rank",
+    "hits@k" for k in ks, "n"}``; ValueError on zero valid rows."""
+    import ctypes
+
+    import torch
+
+    from . import _lib as L
+
+    L.require_cuda(greater, equal)
+    if (greater.dim() != 1 or greater.shape != equal.shape or greater.dtype != torch.int64
+            or equal.dtype != torch.int64):
+        raise ValueError("greater and equal must be int64 vectors of one length")
+    if ties not in RANK_TIES:
+        raise ValueError(f"ties must be one of {sorted(RANK_TIES)}, got {ties!r}")
+    ks = [int(k) for k in ks]
+    if len(ks) > 8 or any(k < 1 for k in ks):
+        raise ValueError("ks: at most 8 values of k >= 1")
+    g, e = greater.contiguous(), equal.contiguous()
+    out = rank_summary(g, e, ks, ties).tolist()
+    hits, valid, sum2r = out[:len(ks)], out[len(ks)], out[len(ks) + 1]
+    rr = ctypes.c_double.from_buffer(ctypes.c_int64(out[len(ks) + 2])).value
+    if valid == 0:
+        raise ValueError("no valid rows to rank")
+    res = {"mrr": rr / valid, "mean_rank": sum2r / (2 * valid), "n": valid}
+    for k, h in zip(ks, hits):
+        res[f"hits@{k}"] = h / valid
+    return res
+
+
+def rank_summary(greater, equal, ks, ties="mean", out=None):
+    """The device half of ``rank_metrics``: an int64 tensor of ``len(ks) + 3`` words -- the
+    hit counts, the valid rows, the sum of 2 * rank and the bits of the fp64 sum of
+    1 / rank.  No host sync: it can be captured into a HIP graph (``out`` reused)."""
+    import ctypes
+
+    import torch
+
+    from . import _lib as L
+    from . import functional as MF
+
+    n, nk = greater.numel(), len(ks)
+    dev = greater.device
+    if out is None:
+        out = torch.empty(nk + 3, dtype=torch.int64, device=dev)
+    ws = MF._workspace(dev, L.fn("msha_rank_summary_workspace_size")(n))
+    kbuf = (ctypes.c_int64 * max(nk, 1))(*ks)
+    L.call("msha_rank_summary", n, greater.data_ptr() if n else None,
+           equal.data_ptr() if n else None, RANK_TIES[ties], ctypes.addressof(kbuf), nk,
+           out.data_ptr(), out.data_ptr() + 8 * (nk + 2), ws.data_ptr(), ws.numel(),
+           L.stream_handle(dev))
+    return out

@@ -202,3 +202,40 @@ class PipelinedScorer:
                 full, work = nxt
         t.cur = (len(batches) - 1) % 2
         return out
+
+
+def rank_sharded(table: ShardedTable, q: torch.Tensor, target: torch.Tensor, rank_fn,
+                 exclude=None):
+    """Filtered rank counts against a sharded table WITHOUT gathering it: ``(greater,
+    equal, logit)`` of the replicated queries ``q`` (B, F) and GLOBAL target rows ``target``
+    (B,), the same on every rank.  ``rank_fn(q, local_rows, target, exclude, col_offset,
+    target_logit)`` -> (greater, equal, logit) is ``functional.rank_inner``'s contract
+    (``check=False``): with ``target_logit`` None a target outside the shard gives -1 / -1
+    and a logit to be ignored.  Every rank first computes the logits of the targets it owns
+    (one call with ``target_logit`` None; the rows of other owners are masked out and the
+    call's counts dropped, so the sharded ranking costs two passes over the shard); ONE
+    all-reduce of (logit bits, ownership flag) gives every rank every target's logit; every
+    rank then counts over its own rows with ``target_logit`` given, and ONE integer
+    all-reduce adds the counts.  ``exclude``: ``(rowptr, col)`` with GLOBAL column numbers;
+    each rank keeps and renumbers its own range.  A target no rank owns comes back as
+    -1 / -1.  Without a process group and world 1 this is the local call."""
+    lo, hi = row_range(table.n, table.world, table.rank)
+    ex = _local_exclude(exclude, lo, hi) if exclude is not None else None
+    local = table.local[: hi - lo]
+    path = table.path()
+    if path == "copy":
+        return rank_fn(q, local, target, ex, lo, None)
+    _, _, own_logit = rank_fn(q, local, target, None, lo, None)
+    own = (target >= lo) & (target < hi)
+    # the fp32 logits ride as their bits (zero where not owned: the sum is the owner's)
+    bits = own_logit.to(torch.float32).contiguous().view(torch.int32).to(torch.int64)
+    both = torch.stack([torch.where(own, bits, torch.zeros_like(bits)), own.to(torch.int64)], 0)
+    dist.all_reduce(both, group=table.group)
+    logit = both[0].to(torch.int32).view(torch.float32)
+    greater, equal, _ = rank_fn(q, local, target, ex, lo, logit)
+    counts = torch.stack([greater, equal], 0)
+    dist.all_reduce(counts, group=table.group)
+    owned = both[1] > 0
+    minus = torch.full_like(counts[0], -1)
+    return (torch.where(owned, counts[0], minus), torch.where(owned, counts[1], minus),
+            torch.where(owned, logit, torch.full_like(logit, float("nan"))))
