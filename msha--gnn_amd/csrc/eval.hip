@@ -12,7 +12,7 @@
 //               so AUC = U2 / (2 P Nn) on the host in fp64.  Integers only on the device:
 //               the result does not depend on the order of execution.
 //
-// rank_auc sorts each column's keys (the order-preserving uint32 image of the fp32 score,
+// rank_auc sorts each column's keys (order_key.h's ra_key of the fp32 score: order-preserving,
 // -0.0 folded onto +0.0; the positive bit rides as a one-byte payload) with a stable LSD
 // radix sort, 8-bit digits, 4 passes.  A column of at most kRaTile keys is sorted in the
 // LDS of one block (one launch for all columns).  Longer columns take, per pass, per-block
@@ -21,6 +21,7 @@
 // sorted order: with the exclusive prefix counts (neg, pos) at a group's start s and the
 // inclusive counts at its end e, the group adds (pos_e - pos_s) * (neg_s + neg_e).
 #include "common.h"
+#include "order_key.h"
 
 namespace msha {
 
@@ -137,13 +138,6 @@ __global__ void __launch_bounds__(kLossWaves* kWave) eval_loss_kernel(
 
 // ----------------------------------------------------------------- rank_auc ----
 
-__device__ __forceinline__ uint32_t ra_key(uint32_t bits) {
-  if (bits == 0x80000000u) bits = 0u;  // -0.0 == +0.0 (denormals stay distinct)
-  return (bits & 0x80000000u) ? ~bits : bits ^ 0x80000000u;
-}
-__device__ __forceinline__ uint32_t ra_bits(uint32_t key) {
-  return (key & 0x80000000u) ? key ^ 0x80000000u : ~key;
-}
 __device__ __forceinline__ uint8_t ra_pos(int64_t label, const int32_t* cls, int k, int binary) {
   if (binary) return label != 0 ? 1 : 0;
   return label == (int64_t)(cls != nullptr ? cls[k] : k) ? 1 : 0;

@@ -5,13 +5,12 @@
 // z_bj = sum_f Q[q_b, f] * T[j, f], without ever writing the (B, n) score matrix and for
 // every K at once (rank = 1 + greater + a share of equal).
 //
-//   rank_inner    topk.hip's main loop with a counting epilogue.  A block owns a tile of 128
-//                 query rows, resident as MFMA A operands (wave w: rows 32 w .. +31, all 64
-//                 candidates of a tile), and streams its range of candidates through the
-//                 double-buffered LDS image in 256-byte row chunks; fp32 tables run
-//                 v_mfma_f32_16x16x4_f32, bf16 tables v_mfma_f32_16x16x32_bf16, a logit is
-//                 one accumulation chain ordered by f alone -- the instruction sequence of
-//                 topk_inner_kernel, so the logits are the ones it reports, bit for bit.
+//   rank_inner    inner_tile.h's streamed tile with a counting epilogue.  A block owns a
+//                 tile of 128 query rows, resident as MFMA A operands (wave w: rows
+//                 32 w .. +31, all 64 candidates of a tile), and streams its range of
+//                 candidates; a logit is one accumulation chain ordered by f alone, through
+//                 the one mma_chunk topk_inner_kernel runs, so the logits are the ones it
+//                 reports, bit for bit.
 //                 Before its range a block stages the rows T[t_b] of its own query tile as
 //                 two gathered candidate tiles, runs them through the same path and keeps the
 //                 diagonal: the target's logit comes from the same chain, a candidate row
@@ -30,63 +29,20 @@
 //   rank_summary  MRR / mean-rank / Hits@K sums of the counts: integers, and one fp64 sum
 //                 in a fixed order (lanes stride, xor tree, waves in order, blocks in order).
 //
-// Order: the uint32 image of topk.hip and eval.hip -- -0.0 folded onto +0.0, +inf highest,
-// every NaN below -inf and all NaNs equal among themselves -- here shifted so that the NaNs
-// are the lowest contiguous range: image = m + 0x807fffff (mod 2^32), m the fp32 bits with
-// the low 31 bits inverted under a set sign.  Integer compares and integer adds only, ordinary
+// Order: order_key.h's rk_image -- topk.hip's order (-0.0 folded onto +0.0, +inf highest,
+// every NaN below -inf and all NaNs equal among themselves) in the shifted form that makes the
+// NaNs the lowest contiguous range.  Integer compares and integer adds only, ordinary
 // vector stores, no atomics: the result does not depend on the order of execution or on the
 // split count.
-#include "common.h"
+#include "inner_tile.h"
+#include "order_key.h"
 
 namespace msha {
 
-typedef float rk_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 rk_bf16x8 __attribute__((ext_vector_type(8)));
+using namespace inner;
 
-constexpr int kRkThreads = 256;
-constexpr int kRkQT = 128;         // query rows per block
-constexpr int kRkCT = 64;          // candidates per tile
-constexpr int kRkNC = kRkCT / 16;  // 16-candidate groups a wave holds
-constexpr int kRkPitch = 272;      // LDS pitch of a 256-byte row chunk (16 B of padding)
-constexpr int kRkChunk = kRkCT * kRkPitch;
-constexpr int kRkCUs = 256;
-constexpr uint32_t kRkNaNTop = 0x00fffffdu;    // every NaN's image is at or below this
-constexpr uint32_t kRkNegZero = 0x807ffffeu;   // image of -0.0; +0.0 is one above
-
-__device__ __forceinline__ uint32_t rk_image(float v) {
-  const uint32_t b = __float_as_uint(v);
-  const uint32_t flip = (uint32_t)((int32_t)b >> 31) >> 1;
-  return (b ^ flip) + 0x807fffffu;
-}
-
-// [lo, hi]: the images that tie with a target of logit z
-__device__ __forceinline__ void rk_bracket(float z, uint32_t* lo, uint32_t* hi) {
-  const uint32_t w = rk_image(z);
-  if (w <= kRkNaNTop) {
-    *lo = 0u;
-    *hi = kRkNaNTop;
-  } else if (w == kRkNegZero || w == kRkNegZero + 1u) {
-    *lo = kRkNegZero;
-    *hi = kRkNegZero + 1u;
-  } else {
-    *lo = w;
-    *hi = w;
-  }
-}
-
-// is candidate j in the ascending exclusion row of query position b
-__device__ __forceinline__ bool rk_excluded(const int32_t* rowptr, const int32_t* col, int64_t b,
-                                            int32_t j) {
-  int32_t lo = rowptr[b];
-  const int32_t end = rowptr[b + 1];
-  int32_t hi = end;
-  while (lo < hi) {
-    const int32_t mid = lo + ((hi - lo) >> 1);
-    if (col[mid] < j) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < end && col[lo] == j;
-}
+constexpr int kRkQT = 128;        // query rows per block
+constexpr int kRkNC = kCT / 16;   // 16-candidate groups a wave holds: all of a tile
 
 struct RkArgs {
   int64_t n_q, rows_q, ldq, ldt, n_cand, col_offset, per_split;
@@ -116,12 +72,9 @@ __device__ __forceinline__ int rk_row_fault(const RkArgs& a, int64_t b, int64_t*
 }
 
 template <typename T, bool EXCL>
-__global__ void __launch_bounds__(kRkThreads, sizeof(T) == 2 ? 2 : 1)
+__global__ void __launch_bounds__(kThreads, sizeof(T) == 2 ? 2 : 1)
     rank_inner_kernel(RkArgs a) {
-  constexpr bool BF = sizeof(T) == 2;
-  constexpr int NSTEP = 256 * (int)sizeof(T) / 64;  // 64-byte steps of a 256-feature row
-  constexpr int NCH = NSTEP / 4;                    // 256-byte chunks of it
-  __shared__ __attribute__((aligned(16))) unsigned char chunks[2 * kRkChunk];
+  __shared__ __attribute__((aligned(16))) unsigned char chunks[2 * kChunk];
   __shared__ int s_tloc[kRkQT];   // the row's target as a local candidate, or -1
   __shared__ int s_live[kRkQT];   // the row has a rank
   __shared__ float s_tz[kRkQT];   // the logit it is ranked against
@@ -133,10 +86,7 @@ __global__ void __launch_bounds__(kRkThreads, sizeof(T) == 2 ? 2 : 1)
   const int rb = w * 32;
   const int64_t q0 = (int64_t)blockIdx.x * kRkQT;
   const int split = blockIdx.y;
-  const int fbytes = a.F * (int)sizeof(T);
-  const int nsteps = (fbytes + 63) / 64, nch = (nsteps + 3) / 4;
-  const unsigned char* Qb = reinterpret_cast<const unsigned char*>(a.Q);
-  const unsigned char* Tb = reinterpret_cast<const unsigned char*>(a.T);
+  const Width wd = width<T>(a.F);
 
   if (tid < kRkQT) {
     const int64_t b = q0 + tid;
@@ -155,66 +105,14 @@ __global__ void __launch_bounds__(kRkThreads, sizeof(T) == 2 ? 2 : 1)
   }
 
   // ---- the query tile: A operands, resident.  Validity is decided from qi[b] alone.
-  uint4 areg[2][NSTEP];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int64_t b = q0 + rb + 16 * r + n;
-    int64_t qrow = -1;
-    if (b < a.n_q) {
-      qrow = a.qi != nullptr ? a.qi[b] : b;
-      if ((uint64_t)qrow >= (uint64_t)a.rows_q) qrow = -1;
-    }
-#pragma unroll
-    for (int s = 0; s < NSTEP; ++s) {
-      const int off = s * 64 + 16 * g;
-      areg[r][s] = (qrow >= 0 && off < fbytes)
-                       ? *reinterpret_cast<const uint4*>(Qb + qrow * a.ldq * (int64_t)sizeof(T) + off)
-                       : make_uint4(0u, 0u, 0u, 0u);
-    }
-  }
+  uint4 areg[2][Geo<T>::NSTEP];
+  int qst[2];
+  load_queries<T>(areg, qst, a.Q, a.qi, a.rows_q, a.ldq, a.n_q, q0 + rb, wd.fbytes);
 
-  // the MFMAs of one staged chunk: topk_inner_kernel's sequence
-  rk_f32x4 acc[2][kRkNC];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < kRkNC; ++c) acc[r][c] = rk_f32x4{0.f, 0.f, 0.f, 0.f};
-  };
-  auto mma_chunk = [&](const unsigned char* img, int ch) {
-#pragma unroll
-    for (int sl = 0; sl < 4; ++sl) {
-      const int s = ch * 4 + sl;
-      if (s < nsteps) {
-        uint4 breg[kRkNC];
-#pragma unroll
-        for (int c = 0; c < kRkNC; ++c)
-          breg[c] = *reinterpret_cast<const uint4*>(img + (16 * c + n) * kRkPitch + sl * 64 + 16 * g);
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-          for (int c = 0; c < kRkNC; ++c) {
-            if (BF) {
-              acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                  __builtin_bit_cast(rk_bf16x8, areg[r][s]),
-                  __builtin_bit_cast(rk_bf16x8, breg[c]), acc[r][c], 0, 0, 0);
-            } else {
-              const uint32_t av[4] = {areg[r][s].x, areg[r][s].y, areg[r][s].z, areg[r][s].w};
-              const uint32_t bv[4] = {breg[c].x, breg[c].y, breg[c].z, breg[c].w};
-#pragma unroll
-              for (int i = 0; i < 4; ++i)
-                acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    __uint_as_float(av[i]), __uint_as_float(bv[i]), acc[r][c], 0, 0, 0);
-            }
-          }
-      }
-    }
-  };
-
-  const int64_t j_begin = (int64_t)split * a.per_split;
-  const int64_t j_end = min(a.n_cand, j_begin + a.per_split);
-  const int64_t ntiles = j_end > j_begin ? (j_end - j_begin + kRkCT - 1) / kRkCT : 0;
-  const int64_t total = ntiles * nch;
+  f32x4 acc[2][kRkNC];
+  const Range rg = split_range(split, a.per_split, a.n_cand);
+  const int64_t j_begin = rg.j_begin, j_end = rg.j_end, ntiles = rg.ntiles;
+  const int64_t total = ntiles * wd.nch;
   uint4 stg[4];
 
   // ---- the targets' own logits: rows T[t_b] of this tile as two gathered candidate tiles;
@@ -222,27 +120,16 @@ __global__ void __launch_bounds__(kRkThreads, sizeof(T) == 2 ? 2 : 1)
   // wave w (gt == w >> 1), group 2 (w & 1) + r, at the lanes with n == 4 g + i
   __syncthreads();
 #pragma unroll 1
-  for (int gt = 0; gt < kRkQT / kRkCT; ++gt) {
-    zero_acc();
+  for (int gt = 0; gt < kRkQT / kCT; ++gt) {
+    zero_acc<kRkNC>(acc);
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      if (ch < nch) {
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int p = tid + kRkThreads * it;
-          const int tl = s_tloc[gt * kRkCT + (p >> 4)];
-          const int off = ch * 256 + (p & 15) * 16;
-          stg[it] = (tl >= 0 && off < fbytes)
-                        ? *reinterpret_cast<const uint4*>(Tb + (int64_t)tl * a.ldt * (int64_t)sizeof(T) + off)
-                        : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int p = tid + kRkThreads * it;
-          *reinterpret_cast<uint4*>(chunks + (p >> 4) * kRkPitch + (p & 15) * 16) = stg[it];
-        }
+    for (int ch = 0; ch < Geo<T>::NCH; ++ch) {
+      if (ch < wd.nch) {
+        load_stage<T>(stg, a.T, a.ldt, wd.fbytes,
+                      [&](int c) -> int64_t { return s_tloc[gt * kCT + c]; }, a.n_cand, ch);
+        store_stage(chunks, stg);
         __syncthreads();
-        mma_chunk(chunks, ch);
+        mma_chunk<T, kRkNC>(acc, areg, chunks, ch, wd.nsteps, 0, n, g);
         __syncthreads();
       }
     }
@@ -286,60 +173,42 @@ __global__ void __launch_bounds__(kRkThreads, sizeof(T) == 2 ? 2 : 1)
       xnext[k] = 0x7fffffff;
       if ((livebits >> k) & 1u) {
         const int64_t b = q0 + rb + 16 * (k >> 2) + 4 * g + (k & 3);
-        int32_t lo_ = a.excl_rowptr[b];
         const int32_t end = a.excl_rowptr[b + 1];
-        int32_t hi_ = end;
-        while (lo_ < hi_) {
-          const int32_t mid = lo_ + ((hi_ - lo_) >> 1);
-          if ((int64_t)a.excl_col[mid] < j_begin) lo_ = mid + 1;
-          else hi_ = mid;
-        }
-        xpos[k] = lo_;
-        if (lo_ < end) xnext[k] = a.excl_col[lo_];
+        xpos[k] = lower_bound(a.excl_col, a.excl_rowptr[b], end, j_begin);
+        if (xpos[k] < end) xnext[k] = a.excl_col[xpos[k]];
       }
     }
   }
 
-  // stage (tile, chunk): 64 rows x 256 bytes, 4 pieces of 16 bytes per thread
-  auto load_stage = [&](int64_t j0, int ch) {
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int p = tid + kRkThreads * it;
-      const int64_t j = j0 + (p >> 4);
-      const int off = ch * 256 + (p & 15) * 16;
-      stg[it] = (j < j_end && off < fbytes)
-                    ? *reinterpret_cast<const uint4*>(Tb + j * a.ldt * (int64_t)sizeof(T) + off)
-                    : make_uint4(0u, 0u, 0u, 0u);
-    }
+  // the streaming loop (its shape is topk_inner_kernel's: stage to LDS, one barrier, the next
+  // stage's loads issued, the chunk's MFMAs under them)
+  auto load = [&](int64_t j0, int ch) {
+    load_stage<T>(stg, a.T, a.ldt, wd.fbytes, [=](int c) { return j0 + c; }, j_end, ch);
   };
-  if (total > 0) load_stage(j_begin, 0);
+  if (total > 0) load(j_begin, 0);
   int64_t it_no = 0;
 
   for (int64_t t = 0; t < ntiles; ++t) {
-    const int64_t j0 = j_begin + t * kRkCT;
-    zero_acc();
+    const int64_t j0 = j_begin + t * kCT;
+    zero_acc<kRkNC>(acc);
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      if (ch < nch) {
-        unsigned char* img = chunks + (it_no & 1) * kRkChunk;
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int p = tid + kRkThreads * it;
-          *reinterpret_cast<uint4*>(img + (p >> 4) * kRkPitch + (p & 15) * 16) = stg[it];
-        }
+    for (int ch = 0; ch < Geo<T>::NCH; ++ch) {
+      if (ch < wd.nch) {
+        unsigned char* img = chunks + (it_no & 1) * kChunk;
+        store_stage(img, stg);
         __syncthreads();
         ++it_no;
         if (it_no < total) {
-          if (ch + 1 < nch) load_stage(j0, ch + 1);
-          else load_stage(j0 + kRkCT, 0);
+          if (ch + 1 < wd.nch) load(j0, ch + 1);
+          else load(j0 + kCT, 0);
         }
-        mma_chunk(img, ch);
+        mma_chunk<T, kRkNC>(acc, areg, img, ch, wd.nsteps, 0, n, g);
       }
     }
 
     // ---- count: C/D layout col = lane & 15 (candidate), row = (lane >> 4) * 4 + reg
-    const int left = (int)min((int64_t)kRkCT, j_end - j0);  // candidates of this tile
-    if (left == kRkCT) {
+    const int left = (int)min((int64_t)kCT, j_end - j0);  // candidates of this tile
+    if (left == kCT) {
 #pragma unroll
       for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -372,7 +241,7 @@ __global__ void __launch_bounds__(kRkThreads, sizeof(T) == 2 ? 2 : 1)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int k = 4 * r + i;
-          while ((int64_t)xnext[k] < j0 + kRkCT) {
+          while ((int64_t)xnext[k] < j0 + kCT) {
             const int32_t cur = xnext[k];
             const int e = (int)(cur - j0);
             if (e >= 0 && e < left && (e & 15) == n) {
@@ -412,7 +281,7 @@ __global__ void __launch_bounds__(kRkThreads, sizeof(T) == 2 ? 2 : 1)
         const int tl = s_tloc[row];
         if (((livebits >> k) & 1u) && tl >= j_begin && tl < j_end) {
           bool counted = true;
-          if (EXCL) counted = !rk_excluded(a.excl_rowptr, a.excl_col, b, tl);
+          if (EXCL) counted = !excluded(a.excl_rowptr, a.excl_col, b, tl);
           if (counted) {
             const uint32_t img = rk_image(s_self[row]);
             cge -= img >= lo[k] ? 1u : 0u;
@@ -428,10 +297,10 @@ __global__ void __launch_bounds__(kRkThreads, sizeof(T) == 2 ? 2 : 1)
 }
 
 // the splits' partial counts -> int64 outputs; rows without a rank -> -1 / -1 and *err
-__global__ void __launch_bounds__(kRkThreads) rank_finish_kernel(RkArgs a, int64_t* out_greater,
+__global__ void __launch_bounds__(kThreads) rank_finish_kernel(RkArgs a, int64_t* out_greater,
                                                                  int64_t* out_equal,
                                                                  int32_t* err) {
-  const int64_t b = (int64_t)blockIdx.x * kRkThreads + threadIdx.x;
+  const int64_t b = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (b >= a.n_q) return;
   int64_t tloc;
   const int fault = rk_row_fault(a, b, &tloc);
@@ -536,18 +405,11 @@ __global__ void __launch_bounds__(kWave) rank_summary_finish_kernel(int nb, int 
   out_rr[0] = rr;
 }
 
-static size_t rk_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static bool rk_supported(int32_t feat, int32_t dtype) {
-  return feat >= 16 && feat <= 256 && feat % 16 == 0 &&
-         (dtype == MSHA_DTYPE_F32 || dtype == MSHA_DTYPE_BF16);
-}
-
 // blocks per CU: 2 for bf16 tables, 1 for fp32 (the kernel's launch bounds)
 static int rk_default_splits(int64_t n_q, int64_t n_cand, int32_t dtype) {
   if (n_q <= 0 || n_cand <= 0) return 1;
   const int64_t tiles = (n_q + kRkQT - 1) / kRkQT;
-  int64_t s = kRkCUs * (dtype == MSHA_DTYPE_BF16 ? 2 : 1) / tiles;
+  int64_t s = kCUs * (dtype == MSHA_DTYPE_BF16 ? 2 : 1) / tiles;
   s = s < n_cand / 512 ? s : n_cand / 512;  // a split has at least 512 candidates
   return (int)(s < 1 ? 1 : s);
 }
@@ -562,18 +424,18 @@ static int rs_blocks(int64_t n) {
 using namespace msha;
 
 extern "C" int msha_rank_inner_supported(int32_t feat, int32_t dtype) {
-  return rk_supported(feat, dtype) ? 1 : 0;
+  return supported(feat, dtype) ? 1 : 0;
 }
 
 extern "C" int msha_rank_inner_splits(int64_t n_q, int64_t n_cand, int32_t feat, int32_t dtype) {
-  if (!rk_supported(feat, dtype)) return 1;
+  if (!supported(feat, dtype)) return 1;
   return rk_default_splits(n_q, n_cand, dtype);
 }
 
 extern "C" size_t msha_rank_inner_workspace_size(int64_t n_q, int64_t n_cand, int32_t splits) {
   if (n_q < 0 || n_cand < 0) return 0;
   if (splits <= 0) splits = rk_default_splits(n_q, n_cand, MSHA_DTYPE_BF16);  // the larger
-  return 256 + rk_align((size_t)n_q * splits * 2 * sizeof(uint32_t));
+  return 256 + align256((size_t)n_q * splits * 2 * sizeof(uint32_t));
 }
 
 extern "C" int msha_rank_inner(int64_t n_q, int32_t feat, int32_t dtype, const void* Q,
@@ -584,30 +446,13 @@ extern "C" int msha_rank_inner(int64_t n_q, int32_t feat, int32_t dtype, const v
                                int32_t splits, int64_t* out_greater, int64_t* out_equal,
                                float* out_logit, int32_t* err, void* ws, size_t ws_bytes,
                                msha_stream_t stream) {
-  MSHA_ARG_CHECK(dtype == MSHA_DTYPE_F32 || dtype == MSHA_DTYPE_BF16,
-                 "rank_inner: dtype must be MSHA_DTYPE_F32 or MSHA_DTYPE_BF16");
-  MSHA_ARG_CHECK(feat >= 16 && feat <= 256 && feat % 16 == 0,
-                 "rank_inner: feat must be a multiple of 16 in [16, 256]");
-  MSHA_ARG_CHECK(n_q >= 0 && n_cand >= 0 && n_cand < (int64_t)0x7fffffff && rows_q >= 0,
-                 "rank_inner: sizes must be non-negative, n_cand below 2^31 - 1");
-  MSHA_ARG_CHECK(splits >= 0 && splits <= 65535, "rank_inner: splits must be in [0, 65535]");
-  MSHA_ARG_CHECK((excl_rowptr == nullptr) == (excl_col == nullptr),
-                 "rank_inner: excl_rowptr and excl_col go together");
-  if (n_q == 0) return MSHA_OK;
-  MSHA_ARG_CHECK(Q != nullptr && target != nullptr && out_greater != nullptr &&
-                     out_equal != nullptr,
-                 "rank_inner: null pointer");
-  MSHA_ARG_CHECK(T != nullptr || n_cand == 0, "rank_inner: null table");
-  MSHA_ARG_CHECK(qi != nullptr || rows_q >= n_q, "rank_inner: rows_q below n_q without qi");
-  const int64_t esz = dtype == MSHA_DTYPE_BF16 ? 2 : 4;
-  MSHA_ARG_CHECK((ldq * esz) % 16 == 0 && (ldt * esz) % 16 == 0 && ldq >= feat &&
-                     (ldt >= feat || n_cand == 0) && ((uintptr_t)Q % 16) == 0 &&
-                     ((uintptr_t)T % 16) == 0,
-                 "rank_inner: tables must be 16-byte aligned with a 16-byte row pitch >= feat");
-  if (splits == 0) splits = rk_default_splits(n_q, n_cand, dtype);
-  const int64_t max_splits = n_cand > 0 ? (n_cand + kRkCT - 1) / kRkCT : 1;
-  if (splits > max_splits) splits = (int32_t)max_splits;
-  const size_t need = rk_align((size_t)n_q * splits * 2 * sizeof(uint32_t));
+  const int rc = check_tables("rank_inner", dtype, true, feat, n_q, n_cand, rows_q, splits,
+                              excl_rowptr, excl_col,
+                              target != nullptr && out_greater != nullptr && out_equal != nullptr,
+                              Q, ldq, qi, T, ldt);
+  if (rc != MSHA_OK || n_q == 0) return rc;
+  splits = clamp_splits(splits, rk_default_splits(n_q, n_cand, dtype), n_cand);
+  const size_t need = align256((size_t)n_q * splits * 2 * sizeof(uint32_t));
   MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= need && ((uintptr_t)ws % 16) == 0,
                  "rank_inner: workspace too small (msha_rank_inner_workspace_size) or unaligned");
   const int64_t tiles = (n_q + kRkQT - 1) / kRkQT;
@@ -619,8 +464,7 @@ extern "C" int msha_rank_inner(int64_t n_q, int32_t feat, int32_t dtype, const v
   a.ldt = ldt;
   a.n_cand = n_cand;
   a.col_offset = col_offset;
-  const int64_t per = (n_cand + splits - 1) / splits;
-  a.per_split = (per + kRkCT - 1) / kRkCT * kRkCT;
+  a.per_split = per_split(n_cand, splits);
   a.Q = Q;
   a.qi = qi;
   a.T = T;
@@ -637,23 +481,23 @@ extern "C" int msha_rank_inner(int64_t n_q, int32_t feat, int32_t dtype, const v
   const bool ex = excl_rowptr != nullptr;
   if (dtype == MSHA_DTYPE_BF16) {
     if (ex)
-      hipLaunchKernelGGL((rank_inner_kernel<bf16_t, true>), grid, dim3(kRkThreads), 0, s, a);
+      hipLaunchKernelGGL((rank_inner_kernel<bf16_t, true>), grid, dim3(kThreads), 0, s, a);
     else
-      hipLaunchKernelGGL((rank_inner_kernel<bf16_t, false>), grid, dim3(kRkThreads), 0, s, a);
+      hipLaunchKernelGGL((rank_inner_kernel<bf16_t, false>), grid, dim3(kThreads), 0, s, a);
   } else {
     if (ex)
-      hipLaunchKernelGGL((rank_inner_kernel<float, true>), grid, dim3(kRkThreads), 0, s, a);
+      hipLaunchKernelGGL((rank_inner_kernel<float, true>), grid, dim3(kThreads), 0, s, a);
     else
-      hipLaunchKernelGGL((rank_inner_kernel<float, false>), grid, dim3(kRkThreads), 0, s, a);
+      hipLaunchKernelGGL((rank_inner_kernel<float, false>), grid, dim3(kThreads), 0, s, a);
   }
-  hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)((n_q + kRkThreads - 1) / kRkThreads)),
-                     dim3(kRkThreads), 0, s, a, out_greater, out_equal, err);
+  hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)((n_q + kThreads - 1) / kThreads)),
+                     dim3(kThreads), 0, s, a, out_greater, out_equal, err);
   return check_launch("rank_inner");
 }
 
 extern "C" size_t msha_rank_summary_workspace_size(int64_t n) {
   if (n < 0) return 0;
-  return 256 + rk_align((size_t)rs_blocks(n) * kRsSlots * sizeof(int64_t));
+  return 256 + align256((size_t)rs_blocks(n) * kRsSlots * sizeof(int64_t));
 }
 
 extern "C" int msha_rank_summary(int64_t n, const int64_t* greater, const int64_t* equal,
@@ -669,7 +513,7 @@ extern "C" int msha_rank_summary(int64_t n, const int64_t* greater, const int64_
                      (n == 0 || (greater != nullptr && equal != nullptr)),
                  "rank_summary: null pointer");
   const int nb = rs_blocks(n);
-  const size_t need = rk_align((size_t)nb * kRsSlots * sizeof(int64_t));
+  const size_t need = align256((size_t)nb * kRsSlots * sizeof(int64_t));
   MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= need && ((uintptr_t)ws % 16) == 0,
                  "rank_summary: workspace too small (msha_rank_summary_workspace_size) or "
                  "unaligned");

@@ -2,12 +2,10 @@
 // for each query row, the K candidates of a table with the highest logit
 // sum_f Q[q, f] * T[j, f], without ever writing the (B, n) score matrix.
 //
-//   topk_inner   a block owns a tile of query rows, resident as MFMA A operands in
-//                registers, and streams its range of candidates through a double-buffered
-//                LDS image in 256-byte row chunks.  fp32 tables run the exact-f32
-//                v_mfma_f32_16x16x4_f32, bf16 tables v_mfma_f32_16x16x32_bf16; either way a
-//                logit is one accumulation chain whose order is fixed by f alone, so it does
-//                not depend on the tile, the block or the column split that computed it.
+//   topk_inner   inner_tile.h's streamed tile (query rows resident as MFMA A operands, the
+//                candidates through a double-buffered LDS image; a logit is one accumulation
+//                chain whose order is fixed by f alone, so it does not depend on the tile,
+//                the block or the column split that computed it) with a selecting epilogue.
 //                After a tile's MFMAs each lane compares its logits with the row's K-th best
 //                key (LDS); survivors are appended to the row's buffer through an LDS
 //                counter.  When a buffer fills, every row with half a buffer or more is
@@ -18,38 +16,21 @@
 //                are cut into chunks and the selections merged again (host loop).
 //
 // Order: (logit descending, index ascending), as ONE integer compare of the key
-// (image << 32) | ~index, where image is eval.hip's order-preserving uint32 image of the
-// fp32 bits with -0.0 folded onto +0.0 and every NaN sent to 1 (below -inf, above "none").
+// (image << 32) | ~index, where image is order_key.h's tk_image: -0.0 folded onto +0.0 and
+// every NaN sent to 1 (below -inf, above "none").
 // Key 0 is "no candidate".  Integer compares only: the result is unique and does not
 // depend on the order of execution.  No float atomics.
-#include "common.h"
+#include "inner_tile.h"
+#include "order_key.h"
 
 namespace msha {
 
+using namespace inner;
 typedef unsigned long long u64;
-typedef float tk_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 tk_bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int kTkThreads = 256;
-constexpr int kTkCT = 64;          // candidates per tile
-constexpr int kTkPitch = 272;      // LDS pitch of a 256-byte row chunk (16 B of padding)
-constexpr int kTkChunk = kTkCT * kTkPitch;
 constexpr int kTkMaxK = 128;
 constexpr int kTkMergeChunk = 4096;  // elements one wave selects from
-constexpr int kTkCUs = 256;
 
-__device__ __forceinline__ uint32_t tk_image(float v) {
-  uint32_t b = __float_as_uint(v);
-  if ((b & 0x7fffffffu) > 0x7f800000u) return 1u;  // NaN: below -inf (0x007fffff)
-  if (b == 0x80000000u) b = 0u;
-  return (b & 0x80000000u) ? ~b : b ^ 0x80000000u;
-}
-__device__ __forceinline__ float tk_value(uint32_t img) {
-  return __uint_as_float((img & 0x80000000u) ? img ^ 0x80000000u : ~img);
-}
-__device__ __forceinline__ u64 tk_key(float v, uint32_t idx) {
-  return ((u64)tk_image(v) << 32) | (u64)(uint32_t)~idx;
-}
 __device__ __forceinline__ void tk_emit(u64 key, int sigmoid, int64_t col_offset, float* val,
                                         int64_t* idx) {
   if (key == 0ull) {
@@ -149,14 +130,11 @@ struct TkArgs {
 // 32 (w >> 1) .. +31 and candidates 32 (w & 1) .. +31 of the tile; QT 32 -> every wave
 // holds all 32 rows and candidates 16 w .. +15.  Per row in LDS: KP sorted keys + KP buffer.
 template <typename T, int KP>
-__global__ void __launch_bounds__(kTkThreads) topk_inner_kernel(TkArgs a) {
+__global__ void __launch_bounds__(kThreads) topk_inner_kernel(TkArgs a) {
   constexpr int QT = KP <= 64 ? 64 : 32;
   constexpr int L = 2 * KP, CAP = KP, EPL = L / 64;
   constexpr int NC = QT == 64 ? 2 : 1;
-  constexpr bool BF = sizeof(T) == 2;
-  constexpr int NSTEP = 256 * (int)sizeof(T) / 64;  // 64-byte steps of a 256-feature row
-  constexpr int NCH = NSTEP / 4;                    // 256-byte chunks of it
-  __shared__ __attribute__((aligned(16))) unsigned char chunks[2 * kTkChunk];
+  __shared__ __attribute__((aligned(16))) unsigned char chunks[2 * kChunk];
   __shared__ u64 lists[QT * L];
   __shared__ u64 thr[QT];
   __shared__ int cnt[QT];
@@ -170,12 +148,9 @@ __global__ void __launch_bounds__(kTkThreads) topk_inner_kernel(TkArgs a) {
   const int cb = QT == 64 ? (w & 1) * 32 : w * 16;
   const int64_t q0 = (int64_t)blockIdx.x * QT;
   const int split = blockIdx.y;
-  const int fbytes = a.F * (int)sizeof(T);
-  const int nsteps = (fbytes + 63) / 64, nch = (nsteps + 3) / 4;
-  const unsigned char* Qb = reinterpret_cast<const unsigned char*>(a.Q);
-  const unsigned char* Tb = reinterpret_cast<const unsigned char*>(a.T);
+  const Width wd = width<T>(a.F);
 
-  for (int i = tid; i < QT * L; i += kTkThreads) lists[i] = 0ull;
+  for (int i = tid; i < QT * L; i += kThreads) lists[i] = 0ull;
   if (tid < QT) cnt[tid] = 0;
   if (tid < 3) flag[tid] = 0;
   int round = 0;
@@ -199,107 +174,49 @@ __global__ void __launch_bounds__(kTkThreads) topk_inner_kernel(TkArgs a) {
   };
 
   // ---- the query tile: A operands, resident.  Validity is decided from qi[b] alone.
-  uint4 areg[2][NSTEP];
+  uint4 areg[2][Geo<T>::NSTEP];
+  int qst[2];
+  load_queries<T>(areg, qst, a.Q, a.qi, a.rows_q, a.ldq, a.n_q, q0 + rb, wd.fbytes);
+  if (g == 0) {
 #pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int row = rb + 16 * r + n;
-    const int64_t b = q0 + row;
-    int64_t qrow = -1;
-    int st = 0;
-    if (b < a.n_q) {
-      qrow = a.qi != nullptr ? a.qi[b] : b;
-      st = 1;
-      if ((uint64_t)qrow >= (uint64_t)a.rows_q) {
-        qrow = -1;
-        st = 2;
-      }
-    }
-    if (g == 0) {
-      state[row] = st;
-      thr[row] = st == 1 ? 0ull : ~0ull;
-      if (st == 2 && a.err != nullptr) atomicOr(a.err, 1);
-    }
-#pragma unroll
-    for (int s = 0; s < NSTEP; ++s) {
-      const int off = s * 64 + 16 * g;
-      areg[r][s] = (qrow >= 0 && off < fbytes)
-                       ? *reinterpret_cast<const uint4*>(Qb + qrow * a.ldq * (int64_t)sizeof(T) + off)
-                       : make_uint4(0u, 0u, 0u, 0u);
+    for (int r = 0; r < 2; ++r) {
+      const int row = rb + 16 * r + n;
+      state[row] = qst[r];
+      thr[row] = qst[r] == 1 ? 0ull : ~0ull;
+      if (qst[r] == 2 && a.err != nullptr) atomicOr(a.err, 1);
     }
   }
 
-  const int64_t j_begin = (int64_t)split * a.per_split;
-  const int64_t j_end = min(a.n_cand, j_begin + a.per_split);
-  const int64_t ntiles = j_end > j_begin ? (j_end - j_begin + kTkCT - 1) / kTkCT : 0;
-  const int64_t total = ntiles * nch;
+  const Range rg = split_range(split, a.per_split, a.n_cand);
+  const int64_t j_begin = rg.j_begin, j_end = rg.j_end, ntiles = rg.ntiles;
+  const int64_t total = ntiles * wd.nch;
 
-  // stage (tile, chunk): 64 rows x 256 bytes, 4 pieces of 16 bytes per thread
+  // the streaming loop (its shape is rank_inner_kernel's: stage to LDS, one barrier, the next
+  // stage's loads issued, the chunk's MFMAs under them)
   uint4 stg[4];
-  auto load_stage = [&](int64_t j0, int ch) {
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int p = tid + kTkThreads * it;
-      const int64_t j = j0 + (p >> 4);
-      const int off = ch * 256 + (p & 15) * 16;
-      stg[it] = (j < j_end && off < fbytes)
-                    ? *reinterpret_cast<const uint4*>(Tb + j * a.ldt * (int64_t)sizeof(T) + off)
-                    : make_uint4(0u, 0u, 0u, 0u);
-    }
+  auto load = [&](int64_t j0, int ch) {
+    load_stage<T>(stg, a.T, a.ldt, wd.fbytes, [=](int c) { return j0 + c; }, j_end, ch);
   };
-  if (total > 0) load_stage(j_begin, 0);
+  if (total > 0) load(j_begin, 0);
   int64_t it_no = 0;
 
   for (int64_t t = 0; t < ntiles; ++t) {
-    const int64_t j0 = j_begin + t * kTkCT;
-    tk_f32x4 acc[2][NC];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) acc[r][c] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
+    const int64_t j0 = j_begin + t * kCT;
+    f32x4 acc[2][NC];
+    zero_acc<NC>(acc);
 
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      if (ch < nch) {
-        unsigned char* img = chunks + (it_no & 1) * kTkChunk;
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int p = tid + kTkThreads * it;
-          *reinterpret_cast<uint4*>(img + (p >> 4) * kTkPitch + (p & 15) * 16) = stg[it];
-        }
+    for (int ch = 0; ch < Geo<T>::NCH; ++ch) {
+      if (ch < wd.nch) {
+        unsigned char* img = chunks + (it_no & 1) * kChunk;
+        store_stage(img, stg);
         __syncthreads();
         ++it_no;
         if (it_no < total) {
-          if (ch + 1 < nch) load_stage(j0, ch + 1);
-          else load_stage(j0 + kTkCT, 0);
+          if (ch + 1 < wd.nch) load(j0, ch + 1);
+          else load(j0 + kCT, 0);
         }
-#pragma unroll
-        for (int sl = 0; sl < 4; ++sl) {
-          const int s = ch * 4 + sl;
-          if (s < nsteps) {
-            uint4 breg[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-              breg[c] = *reinterpret_cast<const uint4*>(img + (cb + 16 * c + n) * kTkPitch +
-                                                        sl * 64 + 16 * g);
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-              for (int c = 0; c < NC; ++c) {
-                if (BF) {
-                  acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                      __builtin_bit_cast(tk_bf16x8, areg[r][s]),
-                      __builtin_bit_cast(tk_bf16x8, breg[c]), acc[r][c], 0, 0, 0);
-                } else {
-                  const uint32_t av[4] = {areg[r][s].x, areg[r][s].y, areg[r][s].z, areg[r][s].w};
-                  const uint32_t bv[4] = {breg[c].x, breg[c].y, breg[c].z, breg[c].w};
-#pragma unroll
-                  for (int i = 0; i < 4; ++i)
-                    acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                        __uint_as_float(av[i]), __uint_as_float(bv[i]), acc[r][c], 0, 0, 0);
-                }
-              }
-          }
-        }
+        mma_chunk<T, NC>(acc, areg, img, ch, wd.nsteps, cb, n, g);
       }
     }
 
@@ -327,13 +244,7 @@ __global__ void __launch_bounds__(kTkThreads) topk_inner_kernel(TkArgs a) {
             if (pend & bit) {
               const int64_t b = q0 + rb + 16 * r + 4 * g + i;
               const int32_t j = (int32_t)(j0 + cb + 16 * c + n);
-              int32_t lo = a.excl_rowptr[b], hi = a.excl_rowptr[b + 1];
-              while (lo < hi) {
-                const int32_t mid = lo + ((hi - lo) >> 1);
-                if (a.excl_col[mid] < j) lo = mid + 1;
-                else hi = mid;
-              }
-              if (lo < a.excl_rowptr[b + 1] && a.excl_col[lo] == j) pend &= ~bit;
+              if (excluded(a.excl_rowptr, a.excl_col, b, j)) pend &= ~bit;
             }
           }
     }
@@ -401,7 +312,7 @@ __global__ void __launch_bounds__(kTkThreads) topk_inner_kernel(TkArgs a) {
 
   // ---- final merge of each row and the stores (ordinary vector stores)
   __syncthreads();
-  for (int row = w; row < QT; row += kTkThreads / kWave) {
+  for (int row = w; row < QT; row += kThreads / kWave) {
     const int st = state[row];
     if (st == 0) continue;
     const int64_t b = q0 + row;
@@ -441,10 +352,10 @@ struct TkMergeArgs {
 // One wave per (row, chunk): registers hold KP best (sorted) + the next KP elements; a
 // batch with nothing above the K-th best so far is skipped without sorting.
 template <int KP>
-__global__ void __launch_bounds__(kTkThreads) topk_merge_kernel(TkMergeArgs m) {
+__global__ void __launch_bounds__(kThreads) topk_merge_kernel(TkMergeArgs m) {
   constexpr int EPL = 2 * KP / 64, H = EPL / 2;
   const int lane = lane_id();
-  const int64_t gw = (int64_t)blockIdx.x * (kTkThreads / kWave) + (threadIdx.x >> 6);
+  const int64_t gw = (int64_t)blockIdx.x * (kThreads / kWave) + (threadIdx.x >> 6);
   if (gw >= m.rows * m.nc) return;
   const int64_t row = gw / m.nc, c = gw % m.nc;
   const int64_t e0 = c * m.chunk, e1 = min(m.n_in, e0 + m.chunk);
@@ -487,16 +398,14 @@ __global__ void __launch_bounds__(kTkThreads) topk_merge_kernel(TkMergeArgs m) {
   }
 }
 
-static size_t tk_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // scratch of the hierarchical selection over rows x n_in elements: two key buffers
 static size_t tk_merge_ws(int64_t rows, int64_t n_in, int k) {
   if (n_in <= kTkMergeChunk) return 0;
   const int64_t n1 = (n_in + kTkMergeChunk - 1) / kTkMergeChunk;
-  size_t bytes = tk_align((size_t)rows * n1 * k * sizeof(u64));
+  size_t bytes = align256((size_t)rows * n1 * k * sizeof(u64));
   if (n1 * k > kTkMergeChunk) {
     const int64_t n2 = (n1 * k + kTkMergeChunk - 1) / kTkMergeChunk;
-    bytes += tk_align((size_t)rows * n2 * k * sizeof(u64));
+    bytes += align256((size_t)rows * n2 * k * sizeof(u64));
   }
   return bytes;
 }
@@ -505,9 +414,9 @@ static void tk_merge_launch(const TkMergeArgs& m, hipStream_t s) {
   const int64_t waves = m.rows * m.nc;
   const dim3 grid((unsigned)((waves + 3) / 4));
   if (m.K <= 64)
-    hipLaunchKernelGGL(topk_merge_kernel<64>, grid, dim3(kTkThreads), 0, s, m);
+    hipLaunchKernelGGL(topk_merge_kernel<64>, grid, dim3(kThreads), 0, s, m);
   else
-    hipLaunchKernelGGL(topk_merge_kernel<128>, grid, dim3(kTkThreads), 0, s, m);
+    hipLaunchKernelGGL(topk_merge_kernel<128>, grid, dim3(kThreads), 0, s, m);
 }
 
 // Top K of rows x n_in elements (keys, or vals + idx) into out_val / out_idx: chunks of
@@ -529,7 +438,7 @@ static void tk_merge_run(int64_t rows, int64_t n_in, int k, const u64* keys, con
   if (n_in > kTkMergeChunk) {
     const int64_t n1 = (n_in + kTkMergeChunk - 1) / kTkMergeChunk;
     buf[0] = reinterpret_cast<u64*>(wb);
-    buf[1] = reinterpret_cast<u64*>(wb + tk_align((size_t)rows * n1 * k * sizeof(u64)));
+    buf[1] = reinterpret_cast<u64*>(wb + align256((size_t)rows * n1 * k * sizeof(u64)));
   }
   int flip = 0;
   while (n_in > kTkMergeChunk) {
@@ -556,15 +465,14 @@ static void tk_merge_run(int64_t rows, int64_t n_in, int k, const u64* keys, con
 }
 
 static bool tk_supported(int32_t feat, int32_t k, int32_t dtype) {
-  return feat >= 16 && feat <= 256 && feat % 16 == 0 && k >= 1 && k <= kTkMaxK &&
-         (dtype == MSHA_DTYPE_F32 || dtype == MSHA_DTYPE_BF16);
+  return supported(feat, dtype) && k >= 1 && k <= kTkMaxK;
 }
 
 static int tk_default_splits(int64_t n_q, int64_t n_cand, int32_t k) {
   if (n_q <= 0 || n_cand <= 0) return 1;
   const int qt = k <= 64 ? 64 : 32;
   const int64_t tiles = (n_q + qt - 1) / qt;
-  int64_t s = kTkCUs / tiles;               // one block per CU
+  int64_t s = kCUs / tiles;               // one block per CU
   s = s < n_cand / 512 ? s : n_cand / 512;  // a split has at least 512 candidates
   return (int)(s < 1 ? 1 : s);
 }
@@ -589,7 +497,7 @@ extern "C" size_t msha_topk_inner_workspace_size(int64_t n_q, int64_t n_cand, in
   if (splits <= 0) splits = tk_default_splits(n_q, n_cand, k);
   size_t bytes = 256;
   if (splits > 1)
-    bytes += tk_align((size_t)n_q * splits * k * sizeof(u64)) +
+    bytes += align256((size_t)n_q * splits * k * sizeof(u64)) +
              tk_merge_ws(n_q, (int64_t)splits * k, k);
   return bytes;
 }
@@ -600,30 +508,12 @@ extern "C" int msha_topk_inner(int64_t n_q, int32_t feat, int32_t dtype, const v
                                const int32_t* excl_rowptr, const int32_t* excl_col, int32_t k,
                                int32_t sigmoid, int32_t splits, float* out_val, int64_t* out_idx,
                                int32_t* err, void* ws, size_t ws_bytes, msha_stream_t stream) {
-  MSHA_ARG_CHECK(dtype == MSHA_DTYPE_F32 || dtype == MSHA_DTYPE_BF16,
-                 "topk_inner: dtype must be MSHA_DTYPE_F32 or MSHA_DTYPE_BF16");
-  MSHA_ARG_CHECK(k >= 1 && k <= kTkMaxK, "topk_inner: k must be in [1, 128]");
-  MSHA_ARG_CHECK(feat >= 16 && feat <= 256 && feat % 16 == 0,
-                 "topk_inner: feat must be a multiple of 16 in [16, 256]");
-  MSHA_ARG_CHECK(n_q >= 0 && n_cand >= 0 && n_cand < (int64_t)0x7fffffff && rows_q >= 0,
-                 "topk_inner: sizes must be non-negative, n_cand below 2^31 - 1");
-  MSHA_ARG_CHECK(splits >= 0 && splits <= 65535, "topk_inner: splits must be in [0, 65535]");
-  MSHA_ARG_CHECK((excl_rowptr == nullptr) == (excl_col == nullptr),
-                 "topk_inner: excl_rowptr and excl_col go together");
-  if (n_q == 0) return MSHA_OK;
-  MSHA_ARG_CHECK(Q != nullptr && out_val != nullptr && out_idx != nullptr,
-                 "topk_inner: null pointer");
-  MSHA_ARG_CHECK(T != nullptr || n_cand == 0, "topk_inner: null table");
-  MSHA_ARG_CHECK(qi != nullptr || rows_q >= n_q, "topk_inner: rows_q below n_q without qi");
-  const int64_t esz = dtype == MSHA_DTYPE_BF16 ? 2 : 4;
-  MSHA_ARG_CHECK((ldq * esz) % 16 == 0 && (ldt * esz) % 16 == 0 && ldq >= feat &&
-                     (ldt >= feat || n_cand == 0) && ((uintptr_t)Q % 16) == 0 &&
-                     ((uintptr_t)T % 16) == 0,
-                 "topk_inner: tables must be 16-byte aligned with a 16-byte row pitch >= feat");
-  if (splits == 0) splits = tk_default_splits(n_q, n_cand, k);
-  const int64_t max_splits = n_cand > 0 ? (n_cand + kTkCT - 1) / kTkCT : 1;
-  if (splits > max_splits) splits = (int32_t)max_splits;
-  const size_t part_bytes = splits > 1 ? tk_align((size_t)n_q * splits * k * sizeof(u64)) : 0;
+  const int rc = check_tables("topk_inner", dtype, k >= 1 && k <= kTkMaxK, feat, n_q, n_cand,
+                              rows_q, splits, excl_rowptr, excl_col,
+                              out_val != nullptr && out_idx != nullptr, Q, ldq, qi, T, ldt);
+  if (rc != MSHA_OK || n_q == 0) return rc;
+  splits = clamp_splits(splits, tk_default_splits(n_q, n_cand, k), n_cand);
+  const size_t part_bytes = splits > 1 ? align256((size_t)n_q * splits * k * sizeof(u64)) : 0;
   const size_t need = splits > 1 ? part_bytes + tk_merge_ws(n_q, (int64_t)splits * k, k) : 0;
   MSHA_ARG_CHECK(need == 0 || (ws != nullptr && ws_bytes >= need && ((uintptr_t)ws % 16) == 0),
                  "topk_inner: workspace too small (msha_topk_inner_workspace_size) or unaligned");
@@ -637,8 +527,7 @@ extern "C" int msha_topk_inner(int64_t n_q, int32_t feat, int32_t dtype, const v
   a.ldt = ldt;
   a.n_cand = n_cand;
   a.col_offset = col_offset;
-  const int64_t per = (n_cand + splits - 1) / splits;
-  a.per_split = (per + kTkCT - 1) / kTkCT * kTkCT;
+  a.per_split = per_split(n_cand, splits);
   a.Q = Q;
   a.qi = qi;
   a.T = T;
@@ -656,14 +545,14 @@ extern "C" int msha_topk_inner(int64_t n_q, int32_t feat, int32_t dtype, const v
   const dim3 grid((unsigned)tiles, (unsigned)splits);
   if (dtype == MSHA_DTYPE_BF16) {
     if (k <= 64)
-      hipLaunchKernelGGL((topk_inner_kernel<bf16_t, 64>), grid, dim3(kTkThreads), 0, s, a);
+      hipLaunchKernelGGL((topk_inner_kernel<bf16_t, 64>), grid, dim3(kThreads), 0, s, a);
     else
-      hipLaunchKernelGGL((topk_inner_kernel<bf16_t, 128>), grid, dim3(kTkThreads), 0, s, a);
+      hipLaunchKernelGGL((topk_inner_kernel<bf16_t, 128>), grid, dim3(kThreads), 0, s, a);
   } else {
     if (k <= 64)
-      hipLaunchKernelGGL((topk_inner_kernel<float, 64>), grid, dim3(kTkThreads), 0, s, a);
+      hipLaunchKernelGGL((topk_inner_kernel<float, 64>), grid, dim3(kThreads), 0, s, a);
     else
-      hipLaunchKernelGGL((topk_inner_kernel<float, 128>), grid, dim3(kTkThreads), 0, s, a);
+      hipLaunchKernelGGL((topk_inner_kernel<float, 128>), grid, dim3(kThreads), 0, s, a);
   }
   if (splits > 1)
     tk_merge_run(n_q, (int64_t)splits * k, k, a.part, nullptr, nullptr, sigmoid, col_offset,

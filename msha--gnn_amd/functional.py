@@ -1121,6 +1121,50 @@ def _topk_k(k) -> int:
     return k
 
 
+def _inner_tables(name, q, table, others=(), k=None):
+    """The table pair of ``topk_inner`` / ``rank_inner``: ``(q, table, Fd, code)`` after
+    their shared checks (``k``: ``topk_inner``'s, checked at its place among them), detached
+    and in a layout the kernels read -- unit stride along a row, 16-byte aligned rows --
+    or else copied contiguous."""
+    if q.dtype != table.dtype:
+        raise TypeError(f"q and table must share a dtype, got {q.dtype} and {table.dtype}")
+    if q.dtype not in (torch.float32, BF16):
+        raise TypeError(f"{name} takes float32 or bfloat16 tables")
+    if q.dim() != 2 or table.dim() != 2 or q.shape[1] != table.shape[1]:
+        raise ValueError(f"q and table must be 2-D with one feature width, got "
+                         f"{tuple(q.shape)} and {tuple(table.shape)}")
+    Fd = q.shape[1]
+    code = _code(q.dtype)
+    shape = (Fd, code) if k is None else (Fd, _topk_k(k), code)
+    _lib.require_cuda(q, table, *others)
+    if not _lib.fn(f"msha_{name}_supported")(*shape):
+        raise ValueError(f"{name}: feature width {Fd} must be a multiple of 16 in [16, 256]")
+    esz = q.element_size()
+
+    def aligned(t):
+        return (t.stride(1) == 1 and (t.stride(0) * esz) % 16 == 0 and t.stride(0) >= Fd
+                and t.data_ptr() % 16 == 0)
+
+    q, table = q.detach(), table.detach()
+    return (q if aligned(q) else q.contiguous(),
+            table if aligned(table) else table.contiguous(), Fd, code)
+
+
+def _inner_exclude(exclude, B):
+    """``exclude`` of ``topk_inner`` / ``rank_inner`` as ``(rowptr, col)`` for the library,
+    ``(None, None)`` without exclusions."""
+    if exclude is None:
+        return None, None
+    rp, cp = exclude
+    _lib.require_cuda(rp, cp)
+    if rp.dtype != torch.int32 or cp.dtype != torch.int32 or rp.numel() != B + 1:
+        raise ValueError("exclude must be (rowptr, col) int32 tensors with B + 1 row "
+                         "pointers (exclude_from_pairs)")
+    if cp.numel() == 0:  # a NULL column list would read as "no exclusion half given"
+        return None, None
+    return rp.contiguous(), cp.contiguous()
+
+
 def topk_inner(q, table, k, rows=None, exclude=None, sigmoid=True, col_offset=0, splits=None,
                check=True):
     """For each query the ``k`` rows of ``table`` with the highest inner product, without
@@ -1143,30 +1187,8 @@ def topk_inner(q, table, k, rows=None, exclude=None, sigmoid=True, col_offset=0,
     the caller vouches for ``rows`` in [0, n): no host sync happens (the call can be
     captured into a HIP graph), and the kernel still bounds every row -- a stray one comes
     back as filler.  Inference only: the outputs are detached."""
-    if q.dtype != table.dtype:
-        raise TypeError(f"q and table must share a dtype, got {q.dtype} and {table.dtype}")
-    if q.dtype not in (torch.float32, BF16):
-        raise TypeError("topk_inner takes float32 or bfloat16 tables")
-    if q.dim() != 2 or table.dim() != 2 or q.shape[1] != table.shape[1]:
-        raise ValueError(f"q and table must be 2-D with one feature width, got "
-                         f"{tuple(q.shape)} and {tuple(table.shape)}")
-    k = _topk_k(k)
-    Fd = q.shape[1]
-    code = _code(q.dtype)
-    _lib.require_cuda(q, table, rows)
-    if not _lib.fn("msha_topk_inner_supported")(Fd, k, code):
-        raise ValueError(f"topk_inner: feature width {Fd} must be a multiple of 16 in [16, 256]")
-    q, table = q.detach(), table.detach()
-    esz = q.element_size()
-
-    def aligned(t):
-        return (t.stride(1) == 1 and (t.stride(0) * esz) % 16 == 0 and t.stride(0) >= Fd
-                and t.data_ptr() % 16 == 0)
-
-    if not aligned(q):
-        q = q.contiguous()
-    if not aligned(table):
-        table = table.contiguous()
+    q, table, Fd, code = _inner_tables("topk_inner", q, table, (rows,), k)
+    k = int(k)
     dev = q.device
     if rows is not None:
         if check:
@@ -1175,16 +1197,7 @@ def topk_inner(q, table, k, rows=None, exclude=None, sigmoid=True, col_offset=0,
         B = rows.numel()
     else:
         B = q.shape[0]
-    rp = cp = None
-    if exclude is not None:
-        rp, cp = exclude
-        _lib.require_cuda(rp, cp)
-        if rp.dtype != torch.int32 or cp.dtype != torch.int32 or rp.numel() != B + 1:
-            raise ValueError("exclude must be (rowptr, col) int32 tensors with B + 1 row "
-                             "pointers (exclude_from_pairs)")
-        rp, cp = rp.contiguous(), cp.contiguous()
-        if cp.numel() == 0:  # a NULL column list would read as "no exclusion half given"
-            rp = cp = None
+    rp, cp = _inner_exclude(exclude, B)
     n = table.shape[0]
     splits = 0 if splits is None else int(splits)
     vals = torch.empty(B, k, dtype=torch.float32, device=dev)
@@ -1251,35 +1264,13 @@ def rank_inner(q, table, target, rows=None, exclude=None, col_offset=0, target_l
     call can be captured into a HIP graph); a stray ``rows[b]`` or a target outside the
     table gives -1 / -1 (and a NaN logit) for that row only.  Inference only: the outputs
     are detached."""
-    if q.dtype != table.dtype:
-        raise TypeError(f"q and table must share a dtype, got {q.dtype} and {table.dtype}")
-    if q.dtype not in (torch.float32, BF16):
-        raise TypeError("rank_inner takes float32 or bfloat16 tables")
-    if q.dim() != 2 or table.dim() != 2 or q.shape[1] != table.shape[1]:
-        raise ValueError(f"q and table must be 2-D with one feature width, got "
-                         f"{tuple(q.shape)} and {tuple(table.shape)}")
-    Fd = q.shape[1]
-    code = _code(q.dtype)
-    _lib.require_cuda(q, table, rows, target, target_logit)
-    if not _lib.fn("msha_rank_inner_supported")(Fd, code):
-        raise ValueError(f"rank_inner: feature width {Fd} must be a multiple of 16 in [16, 256]")
+    q, table, Fd, code = _inner_tables("rank_inner", q, table, (rows, target, target_logit))
     B = rows.numel() if rows is not None else q.shape[0]
     if target.dim() != 1 or target.numel() != B or target.dtype != torch.int64:
         raise ValueError(f"target must be an int64 vector with one entry per query ({B})")
     if target_logit is not None and (target_logit.dtype != torch.float32
                                      or target_logit.dim() != 1 or target_logit.numel() != B):
         raise ValueError(f"target_logit must be a float32 vector with one entry per query ({B})")
-    q, table = q.detach(), table.detach()
-    esz = q.element_size()
-
-    def aligned(t):
-        return (t.stride(1) == 1 and (t.stride(0) * esz) % 16 == 0 and t.stride(0) >= Fd
-                and t.data_ptr() % 16 == 0)
-
-    if not aligned(q):
-        q = q.contiguous()
-    if not aligned(table):
-        table = table.contiguous()
     dev = q.device
     n = table.shape[0]
     col_offset = int(col_offset)
@@ -1295,16 +1286,7 @@ def rank_inner(q, table, target, rows=None, exclude=None, col_offset=0, target_l
     target = target.contiguous()
     if target_logit is not None:
         target_logit = target_logit.detach().contiguous()
-    rp = cp = None
-    if exclude is not None:
-        rp, cp = exclude
-        _lib.require_cuda(rp, cp)
-        if rp.dtype != torch.int32 or cp.dtype != torch.int32 or rp.numel() != B + 1:
-            raise ValueError("exclude must be (rowptr, col) int32 tensors with B + 1 row "
-                             "pointers (exclude_from_pairs)")
-        rp, cp = rp.contiguous(), cp.contiguous()
-        if cp.numel() == 0:  # a NULL column list would read as "no exclusion half given"
-            rp = cp = None
+    rp, cp = _inner_exclude(exclude, B)
     splits = 0 if splits is None else int(splits)
     greater = torch.empty(B, dtype=torch.int64, device=dev)
     equal = torch.empty(B, dtype=torch.int64, device=dev)

@@ -78,14 +78,28 @@ def rnd():
 
 
 @pytest.mark.parametrize("dt", DTYPES)
-def test_rank_consistent_with_topk(cuda, msha, rnd, dt):
+@pytest.mark.parametrize("K", (50, 128))
+@pytest.mark.parametrize("F", (16, 48, 128, 256))
+def test_rank_consistent_with_topk(cuda, msha, rnd, F, K, dt):
     """The K-th entry of topk_inner's list has exactly K better-ordered candidates; those
     are above it or tie with it, so greater <= K <= greater + equal -- and its logit is the
-    listed value, bit for bit.  No tolerance."""
+    listed value, bit for bit.  No tolerance.
+
+    The two kernels meet in every shape of the shared tile: F = 16 and 48 end inside a
+    256-byte chunk, 128 and 256 fill one to four of them; K = 50 runs the top-K kernel's
+    64-row query tile (two 16-candidate groups a wave), K = 128 its 32-row tile (one group),
+    against the rank kernel's four groups.  200 candidates are four candidate tiles, the
+    last ragged; 130 queries two rank tiles, the last ragged.  The fixture's first 200 table
+    rows, cut to F columns (256: the next 200 rows and 130 rows after them as columns
+    128 .. 255 of the table and the queries)."""
     from msha_gnn_amd import functional as MF
 
-    K, B = 128, rnd["B"]
-    q, h = rnd["q"].to(cuda).to(dt), rnd["h"].to(cuda).to(dt)
+    n, B = 200, rnd["B"]
+    h, q = rnd["h"][:n], rnd["q"]
+    if F > rnd["F"]:
+        h = torch.cat([h, rnd["h"][n:2 * n]], 1)
+        q = torch.cat([q, rnd["h"][2 * n:2 * n + B]], 1)
+    q, h = q[:, :F].to(cuda).to(dt), h[:, :F].to(cuda).to(dt)
     vals, idx = MF.topk_inner(q, h, K, sigmoid=False)
     pos = torch.arange(B, device=cuda) % K
     target = idx[torch.arange(B, device=cuda), pos]
