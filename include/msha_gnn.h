@@ -1029,6 +1029,63 @@ MSHA_API int msha_link_bce_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, con
                                const int32_t* plan_ent, const int32_t* plan_chunk_tab, float* dH,
                                void* ws, size_t ws_bytes, msha_stream_t stream);
 
+/* ---- Link-prediction distillation for the inner-product scorer (LLP.py:231-238: a
+ * teacher-matching term added to the label loss) (ABI 16, added) ------------------------
+ * context sample -> plan -> fused rank / KL / probability loss -> table gradient.  As the
+ * training chain above: nothing is read back or allocated, no float atomic, every sum has a
+ * fixed order, so the whole chain can be captured into one HIP graph.
+ *
+ * Context sampler.  context int64 (n_anchors, K), K = walks * hops + n_rand, 1 <= K <= 64.
+ * Walk w < walks starts at v_0 = anchors[a]; at step s < hops, deg is the CSR degree of v_s,
+ * 0 when v_s is outside [0, n_rows), the row is empty or its rowflag (nullable) is set (a
+ * virtual full row has no edges); deg = 0 puts -1 in this and every later slot of the walk,
+ * else v_{s+1} = col[rowptr[v_s] + ((word * deg) >> 32)] goes to slot w * hops + s.  Slot
+ * walks * hops + j is (word * n_nodes) >> 32, -1 when the anchor is outside [0, n_rows).
+ * word = philox(seed, offset, a * K + slot), the offset as msha_negative_sample's (replay
+ * counter in its high word).  No rejection loop; every index is range-checked before a load
+ * goes through it.  n_nodes in [1, 2^31) when n_rand > 0. */
+MSHA_API int msha_context_sample(int64_t n_anchors, int32_t walks, int32_t hops, int32_t n_rand,
+                                 const int64_t* anchors, int64_t n_rows, int64_t n_nodes,
+                                 int64_t n_edges, const int32_t* rowptr, const int32_t* col,
+                                 const uint8_t* rowflag, uint64_t seed, uint64_t offset,
+                                 int64_t* context, msha_stream_t stream); /* (ABI 16, added) */
+/* Fused distillation loss (ABI 16, added).  Per anchor a and slot k < K (2 <= K <= 64):
+ * y_k = <h[anchors[a]], h[context[a, k]]> by msha_link_bce_fwd's own chain (bitwise its z on
+ * the flat pairs); t_k = teacher_logits[a, k], or the same dot on the teacher table (exactly
+ * one of teacher_logits / teacher is non-NULL; the teacher table has its own feat, dtype,
+ * pitch and row count, under the same width rule).  A slot whose anchor or context index is
+ * outside [0, n) (and [0, n_t) with a teacher table) is padding: logit NaN, g 0, in no term,
+ * counted in n_pad[0].  Over an anchor's valid slots:
+ *   L_R = sum_{i<j} max(0, margin - r (y_i - y_j)), r = sign(d) if |d| > margin else 0,
+ *         d = t_i - t_j (one fp32 subtraction and one compare for each decision);
+ *   L_D = sum_k p_k (log p_k - log q_k), p = softmax(t / tau), q = softmax(y / tau);
+ *   L_P = sum_k (sigmoid(y_k) - sigmoid(t_k))^2.
+ * terms[0..2] = (L_R, L_D, L_P) / n_anchors summed over the anchors, loss[0] = w_rank
+ * terms[0] + w_dist terms[1] + w_prob terms[2]; logits (n_anchors, K) fp32 = y; g
+ * (n_anchors, K) fp32 = d loss / d y, its rank part an integer count times w_rank.  L_D, L_P
+ * and their part of g are evaluated in fp64 from the fp32 logits and rounded once.  The
+ * sums are ordered: tiles of 64 anchors, each in a fixed order, then the partials in order.
+ * ws: msha_link_distill_fwd_workspace_size bytes, 16-byte aligned.  n_anchors * K < 2^30. */
+MSHA_API size_t msha_link_distill_fwd_workspace_size(int64_t n_anchors); /* (ABI 16, added) */
+MSHA_API int msha_link_distill_fwd(int64_t n_anchors, int32_t k, int32_t feat, int32_t dtype,
+                                   const void* h, int64_t ld, int64_t n, const int64_t* anchors,
+                                   const int64_t* context, const float* teacher_logits,
+                                   const void* teacher, int32_t t_feat, int32_t t_dtype,
+                                   int64_t t_ld, int64_t n_t, float margin, float tau,
+                                   float w_rank, float w_dist, float w_prob, float* logits,
+                                   float* g, float* loss, float* terms, int32_t* n_pad, void* ws,
+                                   size_t ws_bytes, msha_stream_t stream); /* (ABI 16, added) */
+/* Table gradient from a per-pair factor (ABI 16, added): dH[r] = gloss[0] * sum over row r's
+ * endpoints e in plan order of g[p] h[other(e)], with the pairs (src[p], dst[p]), their plan
+ * and the chunk partials exactly as msha_link_bce_bwd (g loaded instead of recomputed).  dH
+ * (n, feat) fp32, every row written.  ws: msha_pair_grad_bwd_workspace_size bytes. */
+MSHA_API size_t msha_pair_grad_bwd_workspace_size(int64_t n_pairs, int32_t feat); /* (ABI 16, added) */
+MSHA_API int msha_pair_grad_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
+                                int64_t ld, int64_t n, const int64_t* src, const int64_t* dst,
+                                const float* g, const float* gloss, const int32_t* plan_rowptr,
+                                const int32_t* plan_ent, const int32_t* plan_chunk_tab, float* dH,
+                                void* ws, size_t ws_bytes, msha_stream_t stream); /* (ABI 16, added) */
+
 #ifdef __cplusplus
 }
 #endif

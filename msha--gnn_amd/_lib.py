@@ -241,6 +241,16 @@ SIGNATURES = {
     "msha_link_bce_bwd_workspace_size": (SZ, [I64, I32]),
     "msha_link_bce_bwd": (C.c_int, [I64, I32, I32, P, I64, I64, P, P, P, P, P, P, P, P, P, P, P,
                                     SZ, P]),
+    # link-prediction distillation (ABI 16, added)
+    "msha_context_sample": (C.c_int, [I64, I32, I32, I32, P, I64, I64, I64, P, P, P, U64, U64, P,
+                                      P]),
+    "msha_link_distill_fwd_workspace_size": (SZ, [I64]),
+    "msha_link_distill_fwd": (C.c_int, [I64, I32, I32, I32, P, I64, I64, P, P, P, P, I32, I32,
+                                        I64, I64, F32, F32, F32, F32, F32, P, P, P, P, P, P, SZ,
+                                        P]),
+    "msha_pair_grad_bwd_workspace_size": (SZ, [I64, I32]),
+    "msha_pair_grad_bwd": (C.c_int, [I64, I32, I32, P, I64, I64, P, P, P, P, P, P, P, P, P, SZ,
+                                     P]),
 }
 
 _lib = None

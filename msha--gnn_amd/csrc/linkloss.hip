@@ -24,6 +24,7 @@
 // 2 * ceil(2P / C) slots (even: the chunk that starts inside the window, odd: the first
 // chunk of the long row that starts inside it).  A static bound; nothing is read back.
 #include "common.h"
+#include "pair_grad.h"
 
 namespace msha {
 
@@ -32,7 +33,7 @@ typedef unsigned long long u64;
 constexpr int kLlThreads = 256;
 constexpr int kLlWaves = kLlThreads / kWave;
 constexpr int kPlTile = kLlThreads * 16;  // keys per block and radix pass
-constexpr int kPlChunk = 512;             // endpoints per backward chunk
+constexpr int kPlChunk = kPgChunk;        // endpoints per backward chunk (pair_grad.h)
 constexpr int kFwdTile = 1024;            // pairs per forward block (fixes the loss order)
 constexpr int kFinThreads = 1024;
 
@@ -381,20 +382,6 @@ __global__ void __launch_bounds__(kFinThreads) lb_loss_final_kernel(
 
 // ---------------------------------------------------------------- link_bce_bwd ----
 
-template <typename T>
-struct LbArgs {
-  int64_t P, n, ld;
-  int F;
-  const T* h;
-  const int64_t *src, *dst;
-  const float *z, *y, *w;
-  float winv;
-  const float* gloss;
-  const int32_t *rowptr, *ent, *tab;
-  float* part;  // (2 nwin, F) chunk partials
-  float* dH;
-};
-
 // g = gloss w (sigmoid(z) - y) as (1 - y) sigmoid(z) - y sigmoid(-z), in fp64: neither a
 // saturated sigmoid nor a soft target near it cancels
 __device__ __forceinline__ float lb_grad(float z, float y, float w, float gl) {
@@ -406,125 +393,17 @@ __device__ __forceinline__ float lb_grad(float z, float y, float w, float gl) {
   return (float)((double)gl * (double)w * ((1.0 - (double)y) * sp - (double)y * sn));
 }
 
-// sum over the endpoints ent[beg, end) of g h[other], one wave: 64 endpoints' scalars are
-// loaded a lane each, then their rows are gathered 64 / QP at a time (QP lanes x 16 bytes a
-// row).  Endpoint i of the range goes to lane group i % (64 / QP); the groups are added by an
-// xor tree at the end: the order is a function of the range and F alone.  All lanes of a
-// column hold the sum on return.
-template <typename T>
-__device__ __forceinline__ Pk<T> lb_sum_range(const LbArgs<T>& a, int beg, int end) {
-  constexpr int V = Pk<T>::V;
-  constexpr int UNROLL = 4;
-  const int lane = lane_id();
-  const int QP = a.F / V, EPW = kWave / QP;
-  const int slot = lane / QP, q = lane % QP;
-  const float gl = a.gloss[0];
-  Pk<T> acc = pk_zero<T>();
-  for (int base = beg; base < end; base += kWave) {
-    const int pos = base + lane;
-    float g = 0.f;
-    int64_t other = 0;
-    if (pos < end) {
-      const int64_t e = a.ent[pos];
-      if ((uint64_t)e < (uint64_t)(2 * a.P)) {
-        const int64_t p = e < a.P ? e : e - a.P;
-        const int64_t o = e < a.P ? a.dst[p] : a.src[p];
-        if ((uint64_t)o < (uint64_t)a.n) {  // (a plan of another pair list: no stray read)
-          other = o;
-          g = lb_grad(a.z[p], a.y[p], a.w != nullptr ? a.w[p] : a.winv, gl);
-        }
-      }
-    }
-    const int cnt = min(kWave, end - base);
-    for (int j0 = 0; j0 < cnt; j0 += EPW * UNROLL) {
-      float gj[UNROLL];
-      Pk<T> row[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int j = j0 + u * EPW + slot;
-        const float gv = __shfl(g, j & (kWave - 1));
-        const int64_t ov = __shfl(other, j & (kWave - 1));
-        gj[u] = j < cnt ? gv : 0.f;
-        row[u] = j < cnt ? pk_load(a.h + ov * a.ld + V * q) : pk_zero<T>();
-      }
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) acc = pk_fma(gj[u], row[u], acc);
-    }
+// where link_bce_bwd's per-pair factor comes from (pair_grad.h): recomputed from the stored
+// logit, the target and the weight
+struct LbBceG {
+  const float *z, *y, *w;
+  float winv;
+  __device__ __forceinline__ float at(int64_t p, float gl) const {
+    return lb_grad(z[p], y[p], w != nullptr ? w[p] : winv, gl);
   }
-  for (int o = QP; o < kWave; o <<= 1) acc = pk_xor_add(acc, o);
-  return acc;
-}
+};
 
-template <typename T>
-__device__ __forceinline__ void lb_store(float* out, const Pk<T>& acc, int q) {
-  constexpr int V = Pk<T>::V;
-#pragma unroll
-  for (int i = 0; i < V; i += 4)
-    *reinterpret_cast<float4*>(out + V * q + i) =
-        make_float4(acc.v[i], acc.v[i + 1], acc.v[i + 2], acc.v[i + 3]);
-}
-
-// one wave per table row: its first min(deg, C) endpoints; a row of at most C endpoints is
-// complete (zeros for none), a longer one leaves its first chunk's partial
-template <typename T>
-__global__ void __launch_bounds__(kLlThreads) lb_bwd_rows_kernel(LbArgs<T> a) {
-  constexpr int V = Pk<T>::V;
-  const int lane = lane_id();
-  const int QP = a.F / V;
-  const int64_t wave = ((int64_t)blockIdx.x * kLlThreads + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * kLlThreads) >> 6;
-  for (int64_t r = wave; r < a.n; r += nwaves) {
-    int b = a.rowptr[r], e = a.rowptr[r + 1];
-    if (b < 0 || e < b || (int64_t)e > 2 * a.P) b = e = 0;  // (not a plan of this list)
-    const bool lng = e - b > kPlChunk;
-    const Pk<T> acc = lb_sum_range(a, b, lng ? b + kPlChunk : e);
-    float* out = lng ? a.part + (int64_t)(2 * (b / kPlChunk) + 1) * a.F : a.dH + r * a.F;
-    if (lane < QP) lb_store(out, acc, lane);
-  }
-}
-
-// one wave per window: the chunk of a long row that starts in it (not the row's first)
-template <typename T>
-__global__ void __launch_bounds__(kLlThreads) lb_bwd_chunks_kernel(LbArgs<T> a, int64_t nwin) {
-  constexpr int V = Pk<T>::V;
-  const int lane = lane_id();
-  const int QP = a.F / V;
-  const int64_t wave = ((int64_t)blockIdx.x * kLlThreads + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * kLlThreads) >> 6;
-  for (int64_t m = wave; m < nwin; m += nwaves) {
-    const int64_t r = a.tab[2 * m];
-    const int b = a.tab[2 * m + 1];
-    if ((uint64_t)r >= (uint64_t)a.n || b < 0 || b / kPlChunk != m) continue;
-    const int e = min(b + kPlChunk, a.rowptr[r + 1]);
-    if ((int64_t)e > 2 * a.P) continue;  // (not a plan of this list)
-    const Pk<T> acc = lb_sum_range(a, b, e);
-    if (lane < QP) lb_store(a.part + 2 * m * a.F, acc, lane);
-  }
-}
-
-// long rows: the chunk partials added in chunk order (one wave per row, a float4 per lane)
-__global__ void __launch_bounds__(kLlThreads) lb_bwd_finish_kernel(
-    int64_t P, int64_t n, int F, const int32_t* __restrict__ rowptr,
-    const float* __restrict__ part, float* __restrict__ dH) {
-  const int lane = lane_id();
-  const int64_t wave = ((int64_t)blockIdx.x * kLlThreads + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * kLlThreads) >> 6;
-  for (int64_t r = wave; r < n; r += nwaves) {
-    const int b = rowptr[r], e = rowptr[r + 1];
-    if (b < 0 || (int64_t)e > 2 * P || e - b <= kPlChunk) continue;
-    for (int f = 4 * lane; f < F; f += 4 * kWave) {
-      float4 s = *reinterpret_cast<const float4*>(part + (int64_t)(2 * (b / kPlChunk) + 1) * F + f);
-#pragma unroll 8  // the loads of 8 partials in flight; the adds stay in chunk order
-      for (int64_t qp = (int64_t)b + kPlChunk; qp < e; qp += kPlChunk) {
-        const float4 v = *reinterpret_cast<const float4*>(part + 2 * (qp / kPlChunk) * F + f);
-        s = make_float4(s.x + v.x, s.y + v.y, s.z + v.z, s.w + v.w);
-      }
-      *reinterpret_cast<float4*>(dH + r * F + f) = s;
-    }
-  }
-}
-
-static size_t ll_align(size_t x) { return (x + 255) & ~(size_t)255; }
+static size_t ll_align(size_t x) { return pg_align(x); }
 
 struct PlLayout {
   int64_t nb;
@@ -552,15 +431,11 @@ static PlLayout pl_layout(int64_t P) {
   return L;
 }
 
-static int64_t pl_windows(int64_t P) { return P > 0 ? (2 * P + kPlChunk - 1) / kPlChunk : 1; }
+static int64_t pl_windows(int64_t P) { return pg_windows(P); }
 static int64_t fwd_blocks(int64_t P) { return P > 0 ? (P + kFwdTile - 1) / kFwdTile : 1; }
-constexpr int64_t kMaxPairs = ((int64_t)1 << 30) - 1;  // 2P < 2^31
+constexpr int64_t kMaxPairs = kPgMaxPairs;  // 2P < 2^31
 
-static bool lb_width_ok(int32_t feat, int32_t dtype) {
-  if (dtype != MSHA_DTYPE_F32 && dtype != MSHA_DTYPE_BF16) return false;
-  const int v = dtype == MSHA_DTYPE_BF16 ? 8 : 4;
-  return feat >= v && feat <= 64 * v && (feat & (feat - 1)) == 0;
-}
+static bool lb_width_ok(int32_t feat, int32_t dtype) { return pg_width_ok(feat, dtype); }
 
 }  // namespace msha
 
@@ -658,18 +533,7 @@ extern "C" size_t msha_link_bce_bwd_workspace_size(int64_t n_pairs, int32_t feat
 
 static int lb_table_check(const char* name, int64_t n_pairs, int32_t feat, int32_t dtype,
                           const void* h, int64_t ld, int64_t n) {
-  const std::string nm(name);
-  if (n_pairs < 1 || n < 1) return fail(MSHA_ERR_ARG, nm + ": bad sizes (n_pairs >= 1, n >= 1)");
-  if (n_pairs > kMaxPairs) return fail(MSHA_ERR_ARG, nm + ": 2 * n_pairs must be below 2^31");
-  if (!lb_width_ok(feat, dtype))
-    return fail(MSHA_ERR_ARG, nm + ": unsupported width: feat must be a power of two in [16 B, "
-                                   "64 lanes x 16 B] of an fp32 or bf16 table "
-                                   "(msha_link_bce_supported)");
-  const int v = dtype == MSHA_DTYPE_BF16 ? 8 : 4;
-  if (h == nullptr) return fail(MSHA_ERR_ARG, nm + ": null pointer");
-  if (ld < feat || ld % v != 0 || ((uintptr_t)h % 16) != 0)
-    return fail(MSHA_ERR_ARG, nm + ": the table must be 16-byte aligned with a 16-byte row pitch");
-  return MSHA_OK;
+  return pg_table_check(name, n_pairs, feat, dtype, h, ld, n);
 }
 
 extern "C" int msha_link_bce_fwd(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
@@ -702,16 +566,6 @@ extern "C" int msha_link_bce_fwd(int64_t n_pairs, int32_t feat, int32_t dtype, c
   return check_launch("link_bce_fwd");
 }
 
-template <typename T>
-static void lb_bwd_launch(LbArgs<T> a, int64_t nwin, hipStream_t s) {
-  hipLaunchKernelGGL(lb_bwd_rows_kernel<T>, dim3(grid_for(a.n, kLlWaves, 1 << 20)),
-                     dim3(kLlThreads), 0, s, a);
-  hipLaunchKernelGGL(lb_bwd_chunks_kernel<T>, dim3(grid_for(nwin, kLlWaves, 1 << 20)),
-                     dim3(kLlThreads), 0, s, a, nwin);
-  hipLaunchKernelGGL(lb_bwd_finish_kernel, dim3(grid_for(a.n, kLlWaves, 1 << 16)),
-                     dim3(kLlThreads), 0, s, a.P, a.n, a.F, a.rowptr, a.part, a.dH);
-}
-
 extern "C" int msha_link_bce_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
                                  int64_t ld, int64_t n, const int64_t* src, const int64_t* dst,
                                  const float* target, const float* weight, const float* z,
@@ -731,16 +585,15 @@ extern "C" int msha_link_bce_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, c
                  "(msha_link_bce_bwd_workspace_size)");
   hipStream_t s = (hipStream_t)stream;
   const float winv = (float)(1.0 / (double)n_pairs);
+  const LbBceG g = {z, target, weight, winv};
   if (dtype == MSHA_DTYPE_BF16) {
-    const LbArgs<bf16_t> a = {n_pairs, n,      ld,    (int)feat, (const bf16_t*)h, src,
-                              dst,     z,      target, weight,   winv,             gloss,
-                              plan_rowptr, plan_ent, plan_chunk_tab, (float*)ws, dH};
-    lb_bwd_launch(a, nwin, s);
+    const PgArgs<bf16_t, LbBceG> a = {n_pairs, n, ld, (int)feat, (const bf16_t*)h, src, dst, g,
+                                      gloss, plan_rowptr, plan_ent, plan_chunk_tab, (float*)ws, dH};
+    pg_launch(a, nwin, s);
   } else {
-    const LbArgs<float> a = {n_pairs, n,      ld,    (int)feat, (const float*)h, src,
-                             dst,     z,      target, weight,   winv,            gloss,
-                             plan_rowptr, plan_ent, plan_chunk_tab, (float*)ws, dH};
-    lb_bwd_launch(a, nwin, s);
+    const PgArgs<float, LbBceG> a = {n_pairs, n, ld, (int)feat, (const float*)h, src, dst, g,
+                                     gloss, plan_rowptr, plan_ent, plan_chunk_tab, (float*)ws, dH};
+    pg_launch(a, nwin, s);
   }
   return check_launch("link_bce_bwd");
 }

@@ -1,0 +1,190 @@
+// The table gradient of a pair list under its incidence plan (msha_pair_plan), shared by
+// link_bce_bwd (linkloss.hip: g recomputed from the stored logit) and pair_grad_bwd
+// (distill.hip: g loaded):
+//
+//   dH[r] = sum over row r's endpoints e, in plan order, of g_p h[other(e)]
+//
+// One wave per table row; rows longer than a chunk go through chunk partials added in chunk
+// order (the chunk table's layout: linkloss.hip).  No float atomics: the result is a function
+// of the plan alone.  G is where a pair's factor comes from: G::at(p, gloss) -> float.
+#pragma once
+
+#include "common.h"
+
+namespace msha {
+
+constexpr int kPgThreads = 256;
+constexpr int kPgWaves = kPgThreads / kWave;
+constexpr int kPgChunk = 512;  // endpoints per backward chunk (msha_pair_plan_chunk)
+
+template <typename T, typename G>
+struct PgArgs {
+  int64_t P, n, ld;
+  int F;
+  const T* h;
+  const int64_t *src, *dst;
+  G g;
+  const float* gloss;
+  const int32_t *rowptr, *ent, *tab;
+  float* part;  // (2 nwin, F) chunk partials
+  float* dH;
+};
+
+// sum over the endpoints ent[beg, end) of g h[other], one wave: 64 endpoints' scalars are
+// loaded a lane each, then their rows are gathered 64 / QP at a time (QP lanes x 16 bytes a
+// row).  Endpoint i of the range goes to lane group i % (64 / QP); the groups are added by an
+// xor tree at the end: the order is a function of the range and F alone.  All lanes of a
+// column hold the sum on return.
+template <typename T, typename G>
+__device__ __forceinline__ Pk<T> pg_sum_range(const PgArgs<T, G>& a, int beg, int end) {
+  constexpr int V = Pk<T>::V;
+  constexpr int UNROLL = 4;
+  const int lane = lane_id();
+  const int QP = a.F / V, EPW = kWave / QP;
+  const int slot = lane / QP, q = lane % QP;
+  const float gl = a.gloss[0];
+  Pk<T> acc = pk_zero<T>();
+  for (int base = beg; base < end; base += kWave) {
+    const int pos = base + lane;
+    float g = 0.f;
+    int64_t other = 0;
+    if (pos < end) {
+      const int64_t e = a.ent[pos];
+      if ((uint64_t)e < (uint64_t)(2 * a.P)) {
+        const int64_t p = e < a.P ? e : e - a.P;
+        const int64_t o = e < a.P ? a.dst[p] : a.src[p];
+        if ((uint64_t)o < (uint64_t)a.n) {  // (a plan of another pair list: no stray read)
+          other = o;
+          g = a.g.at(p, gl);
+        }
+      }
+    }
+    const int cnt = min(kWave, end - base);
+    for (int j0 = 0; j0 < cnt; j0 += EPW * UNROLL) {
+      float gj[UNROLL];
+      Pk<T> row[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int j = j0 + u * EPW + slot;
+        const float gv = __shfl(g, j & (kWave - 1));
+        const int64_t ov = __shfl(other, j & (kWave - 1));
+        gj[u] = j < cnt ? gv : 0.f;
+        row[u] = j < cnt ? pk_load(a.h + ov * a.ld + V * q) : pk_zero<T>();
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) acc = pk_fma(gj[u], row[u], acc);
+    }
+  }
+  for (int o = QP; o < kWave; o <<= 1) acc = pk_xor_add(acc, o);
+  return acc;
+}
+
+template <typename T>
+__device__ __forceinline__ void pg_store(float* out, const Pk<T>& acc, int q) {
+  constexpr int V = Pk<T>::V;
+#pragma unroll
+  for (int i = 0; i < V; i += 4)
+    *reinterpret_cast<float4*>(out + V * q + i) =
+        make_float4(acc.v[i], acc.v[i + 1], acc.v[i + 2], acc.v[i + 3]);
+}
+
+// one wave per table row: its first min(deg, C) endpoints; a row of at most C endpoints is
+// complete (zeros for none), a longer one leaves its first chunk's partial
+template <typename T, typename G>
+__global__ void __launch_bounds__(kPgThreads) pg_rows_kernel(PgArgs<T, G> a) {
+  constexpr int V = Pk<T>::V;
+  const int lane = lane_id();
+  const int QP = a.F / V;
+  const int64_t wave = ((int64_t)blockIdx.x * kPgThreads + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * kPgThreads) >> 6;
+  for (int64_t r = wave; r < a.n; r += nwaves) {
+    int b = a.rowptr[r], e = a.rowptr[r + 1];
+    if (b < 0 || e < b || (int64_t)e > 2 * a.P) b = e = 0;  // (not a plan of this list)
+    const bool lng = e - b > kPgChunk;
+    const Pk<T> acc = pg_sum_range(a, b, lng ? b + kPgChunk : e);
+    float* out = lng ? a.part + (int64_t)(2 * (b / kPgChunk) + 1) * a.F : a.dH + r * a.F;
+    if (lane < QP) pg_store(out, acc, lane);
+  }
+}
+
+// one wave per window: the chunk of a long row that starts in it (not the row's first)
+template <typename T, typename G>
+__global__ void __launch_bounds__(kPgThreads) pg_chunks_kernel(PgArgs<T, G> a, int64_t nwin) {
+  constexpr int V = Pk<T>::V;
+  const int lane = lane_id();
+  const int QP = a.F / V;
+  const int64_t wave = ((int64_t)blockIdx.x * kPgThreads + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * kPgThreads) >> 6;
+  for (int64_t m = wave; m < nwin; m += nwaves) {
+    const int64_t r = a.tab[2 * m];
+    const int b = a.tab[2 * m + 1];
+    if ((uint64_t)r >= (uint64_t)a.n || b < 0 || b / kPgChunk != m) continue;
+    const int e = min(b + kPgChunk, a.rowptr[r + 1]);
+    if ((int64_t)e > 2 * a.P) continue;  // (not a plan of this list)
+    const Pk<T> acc = pg_sum_range(a, b, e);
+    if (lane < QP) pg_store(a.part + 2 * m * a.F, acc, lane);
+  }
+}
+
+// long rows: the chunk partials added in chunk order (one wave per row, a float4 per lane)
+static __global__ void __launch_bounds__(kPgThreads) pg_finish_kernel(
+    int64_t P, int64_t n, int F, const int32_t* __restrict__ rowptr,
+    const float* __restrict__ part, float* __restrict__ dH) {
+  const int lane = lane_id();
+  const int64_t wave = ((int64_t)blockIdx.x * kPgThreads + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * kPgThreads) >> 6;
+  for (int64_t r = wave; r < n; r += nwaves) {
+    const int b = rowptr[r], e = rowptr[r + 1];
+    if (b < 0 || (int64_t)e > 2 * P || e - b <= kPgChunk) continue;
+    for (int f = 4 * lane; f < F; f += 4 * kWave) {
+      float4 s = *reinterpret_cast<const float4*>(part + (int64_t)(2 * (b / kPgChunk) + 1) * F + f);
+#pragma unroll 8  // the loads of 8 partials in flight; the adds stay in chunk order
+      for (int64_t qp = (int64_t)b + kPgChunk; qp < e; qp += kPgChunk) {
+        const float4 v = *reinterpret_cast<const float4*>(part + 2 * (qp / kPgChunk) * F + f);
+        s = make_float4(s.x + v.x, s.y + v.y, s.z + v.z, s.w + v.w);
+      }
+      *reinterpret_cast<float4*>(dH + r * F + f) = s;
+    }
+  }
+}
+
+static inline size_t pg_align(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline int64_t pg_windows(int64_t P) {
+  return P > 0 ? (2 * P + kPgChunk - 1) / kPgChunk : 1;
+}
+constexpr int64_t kPgMaxPairs = ((int64_t)1 << 30) - 1;  // 2P < 2^31
+
+// feat a power of two spanning 16 bytes to 64 lanes x 16 bytes of an fp32 or bf16 row
+static inline bool pg_width_ok(int32_t feat, int32_t dtype) {
+  if (dtype != MSHA_DTYPE_F32 && dtype != MSHA_DTYPE_BF16) return false;
+  const int v = dtype == MSHA_DTYPE_BF16 ? 8 : 4;
+  return feat >= v && feat <= 64 * v && (feat & (feat - 1)) == 0;
+}
+
+static inline int pg_table_check(const char* name, int64_t n_pairs, int32_t feat, int32_t dtype,
+                                 const void* h, int64_t ld, int64_t n) {
+  const std::string nm(name);
+  if (n_pairs < 1 || n < 1) return fail(MSHA_ERR_ARG, nm + ": bad sizes (n_pairs >= 1, n >= 1)");
+  if (n_pairs > kPgMaxPairs) return fail(MSHA_ERR_ARG, nm + ": 2 * n_pairs must be below 2^31");
+  if (!pg_width_ok(feat, dtype))
+    return fail(MSHA_ERR_ARG, nm + ": unsupported width: feat must be a power of two in [16 B, "
+                                   "64 lanes x 16 B] of an fp32 or bf16 table "
+                                   "(msha_link_bce_supported)");
+  const int v = dtype == MSHA_DTYPE_BF16 ? 8 : 4;
+  if (h == nullptr) return fail(MSHA_ERR_ARG, nm + ": null pointer");
+  if (ld < feat || ld % v != 0 || ((uintptr_t)h % 16) != 0)
+    return fail(MSHA_ERR_ARG, nm + ": the table must be 16-byte aligned with a 16-byte row pitch");
+  return MSHA_OK;
+}
+
+template <typename T, typename G>
+static void pg_launch(const PgArgs<T, G>& a, int64_t nwin, hipStream_t s) {
+  hipLaunchKernelGGL((pg_rows_kernel<T, G>), dim3(grid_for(a.n, kPgWaves, 1 << 20)),
+                     dim3(kPgThreads), 0, s, a);
+  hipLaunchKernelGGL((pg_chunks_kernel<T, G>), dim3(grid_for(nwin, kPgWaves, 1 << 20)),
+                     dim3(kPgThreads), 0, s, a, nwin);
+  hipLaunchKernelGGL(pg_finish_kernel, dim3(grid_for(a.n, kPgWaves, 1 << 16)), dim3(kPgThreads),
+                     0, s, a.P, a.n, a.F, a.rowptr, a.part, a.dH);
+}
+
+}  // namespace msha

@@ -1487,6 +1487,218 @@ def link_bce_loss(h, src, dst, target, weight=None, plan=None, return_logits=Fal
     return (loss, z) if return_logits else loss
 
 
+# ------------------------------------------------- link-prediction distillation ---
+MAX_CONTEXT = 64  # context slots per anchor (one lane each)
+
+
+def sample_context(graph, anchors, walks: int, hops: int, n_rand: int = 0,
+                   n_nodes: int | None = None, seed: int | None = None, offset: int = 0):
+    """The context nodes LLP distils over: int64 ``(A, K)``, ``K = walks * hops + n_rand``
+    (1 <= K <= 64).  Walk ``w`` starts at ``anchors[a]`` and takes ``hops`` uniform steps
+    along the CSR (``--ps_method nb``: hops = 1, ``rw``: hops > 1); slot ``w * hops + s``
+    holds the node after step ``s``, and -1 from the first step out of a node without edges
+    on (outside the CSR's rows, an empty row, a virtual full row).  The last ``n_rand`` slots
+    are uniform over ``[0, n_nodes)`` (default: the graph's columns; needed with a bare CSR),
+    -1 for an anchor outside the CSR's rows.  ``graph``: a ``Graph`` or ``(rowptr, col[,
+    rowflag])`` int32 CSR tensors.  Duplicates and the anchor itself may appear, as in LLP.
+    One Philox word per slot under (``seed``, ``offset``) and the installed replay counter
+    (``set_rng_counter``): a captured graph draws a fresh context on every replay; nothing is
+    read back (``msha_context_sample``)."""
+    if isinstance(graph, Graph):
+        rowptr, col, rowflag, cols = graph.rowptr, graph.col, graph.rowflag, graph.n_cols
+    else:
+        rowptr, col = graph[0], graph[1]
+        rowflag = graph[2] if len(graph) > 2 else None
+        cols = None
+    walks, hops, n_rand = int(walks), int(hops), int(n_rand)
+    if walks < 0 or hops < 0 or n_rand < 0:
+        raise ValueError("sample_context: walks, hops and n_rand must not be negative")
+    K = walks * hops + n_rand
+    if not 1 <= K <= MAX_CONTEXT:
+        raise ValueError(f"sample_context: K = walks * hops + n_rand must be in [1, "
+                         f"{MAX_CONTEXT}], got {K}")
+    if n_nodes is None:
+        if cols is None and n_rand > 0:
+            raise ValueError("sample_context: n_nodes is needed with a bare CSR")
+        n_nodes = cols if cols is not None else 1
+    n_nodes = int(n_nodes)
+    if n_rand > 0 and not 1 <= n_nodes < 2 ** 31:
+        raise ValueError(f"sample_context: n_nodes must be in [1, 2^31), got {n_nodes}")
+    if anchors.dtype != torch.int64 or anchors.dim() != 1:
+        raise TypeError("sample_context: anchors must be a 1-D int64 tensor")
+    if rowptr.dtype != torch.int32 or col.dtype != torch.int32 or rowptr.numel() < 1:
+        raise TypeError("sample_context: the CSR is (rowptr, col) int32 tensors")
+    if rowflag is not None and (rowflag.dtype not in (torch.uint8, torch.bool)
+                                or rowflag.numel() != rowptr.numel() - 1):
+        raise TypeError("sample_context: rowflag is one uint8 per CSR row")
+    _lib.require_cuda(anchors, rowptr, col, rowflag)
+    anchors, rowptr, col = anchors.contiguous(), rowptr.contiguous(), col.contiguous()
+    if rowflag is not None:
+        rowflag = rowflag.contiguous()
+    if seed is None:
+        seed = new_seed()
+    A, dev = anchors.numel(), anchors.device
+    ctx = torch.empty(A, K, dtype=torch.int64, device=dev)
+    _lib.call("msha_context_sample", A, walks, hops, n_rand, anchors.data_ptr() if A else None,
+              rowptr.numel() - 1, n_nodes, col.numel(), rowptr.data_ptr(),
+              col.data_ptr() if col.numel() else None, _lib.ptr(rowflag), int(seed), int(offset),
+              ctx.data_ptr() if A else None, _stream(anchors))
+    return ctx
+
+
+def _context_lists(anchors, context, what):
+    if anchors.dtype != torch.int64 or context.dtype != torch.int64:
+        raise TypeError(f"{what}: anchors and context must be int64 index tensors")
+    if anchors.dim() != 1 or context.dim() != 2 or context.shape[0] != anchors.numel():
+        raise ValueError(f"{what}: anchors must be (A,) and context (A, K), got "
+                         f"{tuple(anchors.shape)} and {tuple(context.shape)}")
+    if 2 * context.numel() >= 2 ** 31:
+        raise ValueError(f"{what}: 2 * A * K must be below 2^31, got A * K = {context.numel()}")
+
+
+def context_plan(anchors, context, n: int) -> PairPlan:
+    """The ``PairPlan`` of the flat pairs ``(anchors[p // K], context.flat[p])`` over ``n``
+    table rows (``pair_plan``); it carries the flat ``src`` it built.  Valid for as long as
+    ``(anchors, context)`` is unchanged."""
+    _context_lists(anchors, context, "context_plan")
+    if anchors.device != context.device:
+        raise ValueError("context_plan: anchors and context must be on one device")
+    A, K = context.shape
+    src = anchors.reshape(A, 1).expand(A, K).reshape(-1)  # a copy: (A K,)
+    plan = pair_plan(src, context.reshape(-1), n)
+    plan.src = src
+    return plan
+
+
+class _LinkDistill(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, anchors, context, tl, th, margin, tau, w_rank, w_dist, w_prob, plan):
+        dt = h.dtype
+
+        def aligned(t):
+            esz = t.element_size()
+            ok = t.stride(1) == 1 and (t.stride(0) * esz) % 16 == 0 and t.data_ptr() % 16 == 0
+            return t if ok else t.contiguous()
+
+        hh = aligned(h.detach())
+        n, Fd = hh.shape
+        A, K = context.shape
+        dev, s = hh.device, _stream(hh)
+        if th is not None:
+            th = aligned(th)
+            t_args = (th.data_ptr(), th.shape[1], _code(th.dtype), th.stride(0), th.shape[0])
+        else:
+            t_args = (None, 0, 0, 0, 0)
+        logits = torch.empty(A, K, dtype=torch.float32, device=dev)
+        g = torch.empty(A, K, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        terms = torch.empty(3, dtype=torch.float32, device=dev)
+        npad = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = _workspace(dev, _lib.fn("msha_link_distill_fwd_workspace_size")(A))
+        _lib.call("msha_link_distill_fwd", A, K, Fd, _code(dt), hh.data_ptr(), hh.stride(0), n,
+                  anchors.data_ptr(), context.data_ptr(), _lib.ptr(tl), *t_args, margin, tau,
+                  w_rank, w_dist, w_prob, logits.data_ptr(), g.data_ptr(), loss.data_ptr(),
+                  terms.data_ptr(), npad.data_ptr(), ws.data_ptr(), ws.numel(), s)
+        ctx.plan, ctx.dt = plan, dt
+        ctx.save_for_backward(hh, context, g)
+        ctx.mark_non_differentiable(terms, logits, npad)
+        return loss, terms, logits, npad
+
+    @staticmethod
+    def backward(ctx, gloss, _gt=None, _gz=None, _gpad=None):
+        hh, context, g = ctx.saved_tensors
+        n, Fd = hh.shape
+        P, dev = context.numel(), hh.device
+        plan = ctx.plan
+        gl = gloss.detach().to(torch.float32).reshape(1).contiguous()
+        dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
+        ws = _workspace(dev, _lib.fn("msha_pair_grad_bwd_workspace_size")(P, Fd))
+        _lib.call("msha_pair_grad_bwd", P, Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n,
+                  plan.src.data_ptr(), context.data_ptr(), g.data_ptr(), gl.data_ptr(),
+                  plan.rowptr.data_ptr(), plan.ent.data_ptr(), plan.chunk_tab.data_ptr(),
+                  dH.data_ptr(), ws.data_ptr(), ws.numel(), _stream(hh))
+        return ((dH if ctx.dt == torch.float32 else dH.to(ctx.dt)),) + (None,) * 10
+
+
+def link_distill_loss(h, anchors, context, *, teacher_logits=None, teacher_table=None,
+                      margin: float = 0.1, tau: float = 1.0, w_rank: float = 1.0,
+                      w_dist: float = 1.0, w_prob: float = 0.0, plan=None, return_terms=False,
+                      return_logits=False):
+    """LLP's teacher-matching loss of the inner-product student logits
+    ``y[a, k] = <h[anchors[a]], h[context[a, k]]>`` against teacher logits ``t[a, k]``
+    (``teacher_logits`` (A, K), or the same inner product on ``teacher_table`` (n_t, F_t);
+    exactly one of the two; never differentiated), fused with the gather:
+
+        L_R = sum_{i<j} F.margin_ranking_loss(y_i, y_j, r_ij, margin, "sum"),
+              r_ij = sign(t_i - t_j) where |t_i - t_j| > margin, else 0       (rank-based)
+        L_D = F.kl_div(log_softmax(y / tau), softmax(t / tau), "sum")        (distribution)
+        L_P = sum (sigmoid(y) - sigmoid(t))^2                 (LLP.py:238's KD_p MSE, summed)
+        loss = (w_rank L_R + w_dist L_D + w_prob L_P) / A
+
+    ``h`` (n, F) float32 or bfloat16 under ``link_bce_loss``'s width rule; ``anchors`` int64
+    (A,); ``context`` int64 (A, K), 2 <= K <= 64 (``sample_context``).  A slot whose anchor or
+    context index is outside the table(s) is padding: it enters no term and shows NaN in the
+    logits.  Returns the fp32 scalar loss, then ``terms`` (3,) = (L_R, L_D, L_P) / A with
+    ``return_terms`` and the (A, K) logits with ``return_logits``.
+
+    The gradient goes to ``h`` only, summed per table row in the order of ``plan``
+    (``context_plan(anchors, context, n)``, built here when None and a gradient is needed)
+    with no float atomics: bitwise reproducible, nothing (A, K, F)-sized is materialised and
+    nothing is read back, so sample + plan + loss + backward capture into one HIP graph."""
+    if h.dtype not in (torch.float32, BF16):
+        raise TypeError(f"link_distill_loss takes a float32 or bfloat16 table, got {h.dtype}")
+    if h.dim() != 2:
+        raise ValueError(f"link_distill_loss: h must be (n, F), got {tuple(h.shape)}")
+    _context_lists(anchors, context, "link_distill_loss")
+    A, K = context.shape
+    if A < 1 or h.shape[0] < 1:
+        raise ValueError("link_distill_loss: needs at least one anchor and one table row")
+    if not 2 <= K <= MAX_CONTEXT:
+        raise ValueError(f"link_distill_loss: K must be in [2, {MAX_CONTEXT}], got {K}")
+    if (teacher_logits is None) == (teacher_table is None):
+        raise ValueError("link_distill_loss: give exactly one of teacher_logits and "
+                         "teacher_table")
+    if teacher_logits is not None and (not teacher_logits.is_floating_point()
+                                       or teacher_logits.shape != (A, K)):
+        raise ValueError(f"link_distill_loss: teacher_logits must be a float tensor of shape "
+                         f"({A}, {K}), got {teacher_logits.dtype} {tuple(teacher_logits.shape)}")
+    if teacher_table is not None:
+        if teacher_table.dtype not in (torch.float32, BF16):
+            raise TypeError(f"link_distill_loss takes a float32 or bfloat16 teacher table, got "
+                            f"{teacher_table.dtype}")
+        if teacher_table.dim() != 2 or teacher_table.shape[0] < 1:
+            raise ValueError(f"link_distill_loss: teacher_table must be (n_t, F_t), got "
+                             f"{tuple(teacher_table.shape)}")
+    margin, tau = float(margin), float(tau)
+    if not tau > 0.0:
+        raise ValueError(f"link_distill_loss: tau must be positive, got {tau}")
+    if not margin >= 0.0:
+        raise ValueError(f"link_distill_loss: margin must not be negative, got {margin}")
+    if plan is not None and (not isinstance(plan, PairPlan) or plan.n != h.shape[0]
+                             or plan.n_pairs != A * K or getattr(plan, "src", None) is None):
+        raise ValueError("link_distill_loss: plan is not a context_plan of this context and "
+                         "table")
+    for t in (h, teacher_table):
+        if t is not None and not _lib.fn("msha_link_bce_supported")(t.shape[1], _code(t.dtype)):
+            raise ValueError(f"link_distill_loss: feature width {t.shape[1]} of a {t.dtype} "
+                             f"table is not supported (a power of two, 16 bytes to 64 lanes x "
+                             f"16 bytes)")
+    for t in (anchors, context, teacher_logits, teacher_table):
+        if t is not None and t.device != h.device:
+            raise ValueError("link_distill_loss: every tensor must be on the table's device")
+    _lib.require_cuda(h)
+    anchors, context = anchors.contiguous(), context.contiguous()
+    tl = (teacher_logits.detach().to(torch.float32).contiguous()
+          if teacher_logits is not None else None)
+    th = teacher_table.detach() if teacher_table is not None else None
+    if plan is None and h.requires_grad and torch.is_grad_enabled():
+        plan = context_plan(anchors, context, h.shape[0])  # only a backward reads it
+    loss, terms, logits, _ = _LinkDistill.apply(h, anchors, context, tl, th, margin, tau,
+                                                float(w_rank), float(w_dist), float(w_prob), plan)
+    out = (loss,) + ((terms,) if return_terms else ()) + ((logits,) if return_logits else ())
+    return out if len(out) > 1 else loss
+
+
 # --------------------------------------------------------- full MSHA layer (Ours) ---
 # the bipartite kernels' block-partial reduce rides in the Ours layer's prep / finish
 # launches (msha_bip_defer_reduce; one graph node fewer each way); MSHA_BIP_DEFER=0: separate

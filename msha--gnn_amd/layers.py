@@ -364,6 +364,21 @@ class LinkPredictor(torch.nn.Module):
                              f"so there is no scalar to rank by")
         return MF.link_bce_loss(h, src, dst, target, weight=weight, plan=plan)
 
+    def distill_loss(self, h, anchors, context, teacher_logits=None, teacher_h=None, **kw):
+        """LLP's teacher-matching loss (LLP.py:231-238) of this predictor's logits of each
+        anchor against its context nodes (``functional.link_distill_loss``: rank-based,
+        distribution-based and probability-matching terms, fused with the gather, with a
+        deterministic gradient to ``h``).  The teacher is its logits ``(A, K)`` or its node
+        table ``teacher_h``, scored by the same inner product.  'inner' only: the
+        reference's 'mlp' head returns a (B, hidden) vector per pair (LLP.py:107-111), which
+        gives no scalar logit to distil."""
+        if self.predictor != "inner":
+            raise ValueError(f"LinkPredictor.distill_loss needs the 'inner' predictor: "
+                             f"{self.predictor!r} scores a pair with a vector (LLP.py:107-115), "
+                             f"so there is no scalar to rank by")
+        return MF.link_distill_loss(h, anchors, context, teacher_logits=teacher_logits,
+                                    teacher_table=teacher_h, **kw)
+
 
 class OursLayer(OursLayer3):
     """Ours.py:29-109: OursLayer3's inter attention plus the intra-source attention
