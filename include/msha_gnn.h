@@ -1086,6 +1086,52 @@ MSHA_API int msha_pair_grad_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, co
                                 const int32_t* plan_ent, const int32_t* plan_chunk_tab, float* dH,
                                 void* ws, size_t ws_bytes, msha_stream_t stream); /* (ABI 16, added) */
 
+/* ---- Representation matching (LLP.py:34-35, :237: KD_cosine(h[rows], t_h[rows]) added to
+ * the student's loss) (ABI 16, added) ---------------------------------------------------
+ * loss[0] = 1 - mean over the valid entries p of cos(h[rows[p]], T[rows[p]]), the teacher T
+ * never differentiated.  Student and teacher are indexed by the same id, so with c_r the
+ * occurrences of r among the valid entries and P_v their number:
+ *   loss  = 1 - (1 / P_v) sum_r c_r cos_r,        cos_r = <h[r], T[r]> / (ns_r nt_r),
+ *   dH[r] = -(gloss / P_v) c_r (T[r] / (ns_r nt_r) - cos_r h[r] / (ns_r |h[r]|)),
+ *   ns_r = max(|h[r]|, 1e-8), nt_r = max(|T[r]|, 1e-8)   (torch's cosine_similarity: each
+ * norm clamped on its own, outside autograd, so the second term keeps the unclamped |h[r]|
+ * of d|h| / dh; it is cos_r h[r] / ns_r^2 above 1e-8 and 0 for a zero row).
+ * h (n, feat) and T (n_t, feat): fp32 or bf16 each, independently; row pitch ld / t_ld
+ * elements, 16-byte aligned rows; feat under msha_link_bce_supported for both dtypes.
+ * rows int64 (n_entries), 1 <= n_entries < 2^31; an entry outside [0, min(n, n_t)) is
+ * padding: it enters nothing and is counted in n_pad[0], decided before any load through
+ * it.  rows NULL: entry p is row p (no histogram pass).  n, n_t < 2^31.
+ * Forward: count is zeroed and filled by exact integer atomics (equal indices of a block
+ * aggregated in LDS first), then one pass over the n table rows; a row that does not occur
+ * reads neither table.  The dot products accumulate in fp32 lanes, the per-row scalars are
+ * fp64.  coef (n, 2) fp32 = (c_r / (P_v ns nt), c_r cos_r / (P_v ns |h[r]|)), zeros for absent
+ * rows; cos_rows (n) fp32, nullable, NaN for absent rows; count (n) int32, nullable.  The
+ * loss sum is ordered: blocks of 1024 table rows, each in a fixed order, then the partials
+ * in order (fp64): a function of the multiset of entries, bitwise reproducible and
+ * invariant under a permutation of rows.  P_v is read on the device; P_v = 0 gives loss 0
+ * and zero coefficients.  ws: msha_link_match_fwd_workspace_size bytes, 16-byte aligned.
+ * Nothing is read back or allocated: capturable. */
+MSHA_API size_t msha_link_match_fwd_workspace_size(int64_t n_entries, int64_t n); /* (ABI 16, added) */
+/* The forward's histogram on its own (ABI 16, added): count (n) int32 is zeroed, then
+ * count[r] = the entries equal to r inside [0, n_valid), n_valid <= n; n_pad[0] = the others. */
+MSHA_API int msha_link_match_count(int64_t n_entries, int64_t n, int64_t n_valid,
+                                   const int64_t* rows, int32_t* count, int32_t* n_pad,
+                                   msha_stream_t stream); /* (ABI 16, added) */
+MSHA_API int msha_link_match_fwd(int64_t n_entries, int32_t feat, int32_t h_dtype, const void* h,
+                                 int64_t ld, int64_t n, int32_t t_dtype, const void* teacher,
+                                 int64_t t_ld, int64_t n_t, const int64_t* rows, float* coef,
+                                 float* cos_rows, int32_t* count, float* loss, int32_t* n_pad,
+                                 void* ws, size_t ws_bytes, msha_stream_t stream); /* (ABI 16, added) */
+/* Its table gradient (ABI 16, added): dH (n, feat) fp32, contiguous, 16-byte aligned,
+ * dH[r] = -gloss[0] (coef[r, 0] T[r] - coef[r, 1] h[r]) with the forward's coef and gloss a
+ * DEVICE scalar.  Every row is written; a row whose coefficients are zero (absent, or
+ * outside the teacher) is written as zeros without a table read.  One streaming pass, no
+ * workspace. */
+MSHA_API int msha_link_match_bwd(int32_t feat, int32_t h_dtype, const void* h, int64_t ld,
+                                 int64_t n, int32_t t_dtype, const void* teacher, int64_t t_ld,
+                                 int64_t n_t, const float* coef, const float* gloss, float* dH,
+                                 msha_stream_t stream); /* (ABI 16, added) */
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,12 @@ SIGNATURES = {
     "msha_pair_grad_bwd_workspace_size": (SZ, [I64, I32]),
     "msha_pair_grad_bwd": (C.c_int, [I64, I32, I32, P, I64, I64, P, P, P, P, P, P, P, P, P, SZ,
                                      P]),
+    # representation matching (ABI 16, added)
+    "msha_link_match_fwd_workspace_size": (SZ, [I64, I64]),
+    "msha_link_match_count": (C.c_int, [I64, I64, I64, P, P, P, P]),
+    "msha_link_match_fwd": (C.c_int, [I64, I32, I32, P, I64, I64, I32, P, I64, I64, P, P, P, P, P,
+                                      P, P, SZ, P]),
+    "msha_link_match_bwd": (C.c_int, [I32, I32, P, I64, I64, I32, P, I64, I64, P, P, P, P]),
 }
 
 _lib = None

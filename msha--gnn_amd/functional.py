@@ -1020,6 +1020,43 @@ def pair_layer(x_i, x_j, W, b, p=0.0, training=False, sigmoid=False, seed=None):
     return _PairLayer.apply(x_i, x_j, W, b, p, seed, sigmoid)
 
 
+class _LinearBias(torch.autograd.Function):
+    """y = x @ W^T + b as one fused launch (msha_pair_linear, act = bias): the student
+    MLP's last layer (LLP.py:78), whose dz is dout itself."""
+
+    @staticmethod
+    def forward(ctx, x, W, b):
+        x, W, b = _f32c(x), _f32c(W), _f32c(b)
+        B, K = x.shape
+        N = W.shape[0]
+        out = torch.empty(B, N, device=x.device, dtype=torch.float32)
+        _lib.call("msha_pair_linear", B, K, N, x.data_ptr(), K, None, None, K, None, B, B,
+                  W.data_ptr(), b.data_ptr(), ACT_BIAS, 0.0, 0, 0, out.data_ptr(), _stream(x))
+        ctx.save_for_backward(x, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, W = ctx.saved_tensors
+        B = x.shape[0]
+        dz = _f32c(dout)
+        dW = gemm(dz.t(), x)                      # (N, K) = dz^T x
+        one = torch.ones(1, device=x.device, dtype=torch.float32)
+        db = gemm(one.as_strided((1, B), (0, 0)), dz).view(-1)  # column sums of dz
+        dx = gemm(dz, W) if ctx.needs_input_grad[0] else None
+        return dx, dW, db
+
+
+def linear_bias(x, W, b):
+    """``F.linear(x, W, b)`` on (B, K) float32 rows as one fused MFMA launch, with the
+    backward on the library's GEMM (``MLP``'s last layer)."""
+    if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[1] or b.shape != (W.shape[0],):
+        raise ValueError(f"linear_bias: x {tuple(x.shape)}, W {tuple(W.shape)}, b "
+                         f"{tuple(b.shape)}")
+    _lib.require_cuda(x, W, b)
+    return _LinearBias.apply(x, W, b)
+
+
 def check_pair_indices(src, dst, rows: int, rows2: int | None = None):
     """torch's ``h[idx]`` index rule for a fused pair gather (LLP.py:233): an index
     outside [-rows, rows) raises IndexError; negative ones inside are wrapped to
@@ -1697,6 +1734,108 @@ def link_distill_loss(h, anchors, context, *, teacher_logits=None, teacher_table
                                                 float(w_rank), float(w_dist), float(w_prob), plan)
     out = (loss,) + ((terms,) if return_terms else ()) + ((logits,) if return_logits else ())
     return out if len(out) > 1 else loss
+
+
+# ------------------------------------------------------ representation matching ---
+def _rows16(t):
+    """``t`` itself when the kernels can read it in place (unit column stride, 16-byte row
+    pitch and base), else a contiguous copy."""
+    esz = t.element_size()
+    ok = t.stride(1) == 1 and (t.stride(0) * esz) % 16 == 0 and t.data_ptr() % 16 == 0
+    return t if ok else t.contiguous()
+
+
+class _LinkMatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, rows, th):
+        dt = h.dtype
+        hh, th = _rows16(h.detach()), _rows16(th)
+        n, Fd = hh.shape
+        P = rows.numel() if rows is not None else n
+        dev, s = hh.device, _stream(hh)
+        coef = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        cos_rows = torch.empty(n, dtype=torch.float32, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        npad = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = _workspace(dev, _lib.fn("msha_link_match_fwd_workspace_size")(P, n))
+        _lib.call("msha_link_match_fwd", P, Fd, _code(dt), hh.data_ptr(), hh.stride(0), n,
+                  _code(th.dtype), th.data_ptr(), th.stride(0), th.shape[0], _lib.ptr(rows),
+                  coef.data_ptr(), cos_rows.data_ptr(), count.data_ptr(), loss.data_ptr(),
+                  npad.data_ptr(), ws.data_ptr(), ws.numel(), s)
+        ctx.dt = dt
+        ctx.save_for_backward(hh, th, coef)
+        ctx.mark_non_differentiable(cos_rows, count, npad)
+        return loss, cos_rows, count, npad
+
+    @staticmethod
+    def backward(ctx, gloss, _gc=None, _gn=None, _gp=None):
+        hh, th, coef = ctx.saved_tensors
+        n, Fd = hh.shape
+        g = gloss.detach().to(torch.float32).reshape(1).contiguous()
+        dH = torch.empty(n, Fd, dtype=torch.float32, device=hh.device)
+        _lib.call("msha_link_match_bwd", Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n,
+                  _code(th.dtype), th.data_ptr(), th.stride(0), th.shape[0], coef.data_ptr(),
+                  g.data_ptr(), dH.data_ptr(), _stream(hh))
+        return (dH if ctx.dt == torch.float32 else dH.to(ctx.dt)), None, None
+
+
+def link_match_loss(h, rows, teacher_table, *, return_rows=False):
+    """LLP's representation-matching term (LLP.py:34-35, :237), fused with the caller's two
+    gathers and with a deterministic table gradient:
+
+        1 - F.cosine_similarity(h[rows], teacher_table[rows].detach(), dim=-1).mean()
+
+    ``h`` (n, F) and ``teacher_table`` (n_t, F): float32 or bfloat16 each, independently,
+    under ``link_bce_loss``'s width rule; ``rows`` int64 (P,).  An entry outside
+    [0, min(n, n_t)) is padding: it enters nothing and the mean is over the others (none:
+    loss 0).  ``rows=None``: row b of ``h`` against row b of ``teacher_table`` (equal row
+    counts), the reference's ``KD_cosine(s, t)`` on tensors already gathered.  Returns the
+    fp32 scalar loss, or ``(loss, cos_rows, count)`` with ``return_rows``: the cosine of
+    every table row (NaN where the row does not occur) and its int32 occurrence count.
+
+    The gradient goes to ``h`` only (a bf16 ``h`` receives it cast from the fp32 row); the
+    teacher is never differentiated.  Every occurrence of a row adds the same cosine and the
+    same gradient row, so the work is an integer histogram of ``rows`` and one pass over the
+    table rows that occur: loss, counts and gradient are a function of the *multiset* of
+    ``rows`` (and the tables) alone -- bitwise reproducible and unchanged by any permutation
+    of ``rows`` -- with no float atomics, nothing (P, F)-sized and nothing read back, so
+    loss + backward can be captured into one HIP graph."""
+    t = teacher_table
+    if h.dtype not in (torch.float32, BF16):
+        raise TypeError(f"link_match_loss takes a float32 or bfloat16 table, got {h.dtype}")
+    if t.dtype not in (torch.float32, BF16):
+        raise TypeError(f"link_match_loss takes a float32 or bfloat16 teacher table, got "
+                        f"{t.dtype}")
+    if h.dim() != 2 or h.shape[0] < 1:
+        raise ValueError(f"link_match_loss: h must be (n, F), got {tuple(h.shape)}")
+    if t.dim() != 2 or t.shape[0] < 1:
+        raise ValueError(f"link_match_loss: teacher_table must be (n_t, F), got "
+                         f"{tuple(t.shape)}")
+    if t.shape[1] != h.shape[1]:
+        raise ValueError(f"link_match_loss: student and teacher must have one width, got "
+                         f"{h.shape[1]} and {t.shape[1]}")
+    if rows is not None:
+        if rows.dtype != torch.int64:
+            raise TypeError("link_match_loss: rows must be an int64 index tensor")
+        if rows.dim() != 1 or not 1 <= rows.numel() < 2 ** 31:
+            raise ValueError(f"link_match_loss: rows must be 1-D with 1 <= P < 2^31, got "
+                             f"{tuple(rows.shape)}")
+    elif t.shape[0] != h.shape[0]:
+        raise ValueError(f"link_match_loss: rows=None needs equal row counts, got "
+                         f"{h.shape[0]} and {t.shape[0]}")
+    for x in (h, t):
+        if not _lib.fn("msha_link_bce_supported")(x.shape[1], _code(x.dtype)):
+            raise ValueError(f"link_match_loss: feature width {x.shape[1]} of a {x.dtype} table "
+                             f"is not supported (a power of two, 16 bytes to 64 lanes x 16 "
+                             f"bytes)")
+    for x in (rows, t):
+        if x is not None and x.device != h.device:
+            raise ValueError("link_match_loss: every tensor must be on the table's device")
+    _lib.require_cuda(h)
+    rows = rows.contiguous() if rows is not None else None
+    loss, cos_rows, count, _ = _LinkMatch.apply(h, rows, t.detach())
+    return (loss, cos_rows, count) if return_rows else loss
 
 
 # --------------------------------------------------------- full MSHA layer (Ours) ---

@@ -10,6 +10,7 @@ and RNG consumption order as the reference, so a model built after
   OursLayer3            Ablation.py:235-277
   ablation3             Ablation.py:279-301  (its heads run as ONE multi-head launch)
   LinkPredictor         LLP.py:86-115
+  MLP                   LLP.py:36-84       (the student encoder; norm_type 'none' only)
   OursLayer, Ours       Ours.py:29-167 (full MSHA: inter + city/province attention)
   GraphConvolution, GCN model.py:11-64     (SpMM over the same CSR/CSC machinery)
 
@@ -275,6 +276,62 @@ class ablation3(nn.Module):  # noqa: N801  (reference class name)
         return _tail_unfused(self, g, u, v)
 
 
+class MLP(nn.Module):
+    """LLP.py:36-84, the student encoder.  Same constructor, submodule names (``layers.N``,
+    ``norms.N``, ``dropout``), state_dict keys and init order as the reference.  With
+    ``norm_type == "none"`` every layer but the last is ONE fused Linear + ReLU + dropout
+    MFMA launch (``functional.pair_layer`` on a single input; Philox masks under the
+    installed replay counter) and the last is one Linear + bias launch
+    (``functional.linear_bias``); the backward runs on the library's GEMM.  ``"batch"`` and
+    ``"layer"`` build the reference's norm submodules, so its checkpoints load, but their
+    forward is not accelerated and raises."""
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio,
+                 norm_type="none"):
+        super().__init__()
+        self.num_layers = num_layers
+        self.norm_type = norm_type
+        self.dropout = nn.Dropout(dropout_ratio)
+        self.layers = nn.ModuleList()
+        self.norms = nn.ModuleList()
+
+        def norm():
+            if self.norm_type == "batch":
+                self.norms.append(nn.BatchNorm1d(hidden_dim))
+            elif self.norm_type == "layer":
+                self.norms.append(nn.LayerNorm(hidden_dim))
+
+        if num_layers == 1:
+            self.layers.append(nn.Linear(input_dim, output_dim))
+        else:
+            self.layers.append(nn.Linear(input_dim, hidden_dim))
+            norm()
+            for _ in range(num_layers - 2):
+                self.layers.append(nn.Linear(hidden_dim, hidden_dim))
+                norm()
+            self.layers.append(nn.Linear(hidden_dim, output_dim))
+
+    def reset_parameters(self):
+        for layer in self.layers:
+            layer.reset_parameters()
+
+    def forward(self, feats):
+        if self.norm_type != "none":
+            # LLP.py:80-81 puts norms[l] between the Linear and the ReLU: not fused here
+            raise NotImplementedError(
+                f"MLP(norm_type={self.norm_type!r}): the BatchNorm1d / LayerNorm between "
+                f"Linear and ReLU (LLP.py:57-60, :64-67, :80-81) is not accelerated; only "
+                f"norm_type='none' runs on the HIP kernels")
+        h = feats
+        for k, layer in enumerate(self.layers):
+            if k != self.num_layers - 1:
+                h = MF.pair_layer(h, None, layer.weight, layer.bias, self.dropout.p,
+                                  self.training)
+            else:
+                h = MF.linear_bias(h, layer.weight, layer.bias)
+        return h
+
+
 class LinkPredictor(torch.nn.Module):
     """LLP.py:86-115.  'mlp': the used layers lins[:-1] each run as ONE fused
     (hadamard) Linear + ReLU + dropout [+ sigmoid] MFMA launch; as in the reference
@@ -378,6 +435,13 @@ class LinkPredictor(torch.nn.Module):
                              f"so there is no scalar to rank by")
         return MF.link_distill_loss(h, anchors, context, teacher_logits=teacher_logits,
                                     teacher_table=teacher_h, **kw)
+
+    def match_loss(self, h, rows, teacher_h):
+        """LLP's representation-matching term ``KD_cosine(h[rows], teacher_h[rows])``
+        (LLP.py:34-35, :237; ``functional.link_match_loss``: a histogram of ``rows`` and one
+        pass over the rows that occur, with a deterministic gradient to ``h``).  It compares
+        node rows, not pair scores, so it is the same for every predictor string."""
+        return MF.link_match_loss(h, rows, teacher_h)
 
 
 class OursLayer(OursLayer3):
