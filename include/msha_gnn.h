@@ -904,6 +904,61 @@ MSHA_API int msha_topk_merge(int64_t rows, int64_t lists, int64_t len, int32_t k
                              float* out_val, int64_t* out_idx, void* ws, size_t ws_bytes,
                              msha_stream_t stream);
 
+/* ---- Select over ragged segments: the attention explanation (Explainer.py:25-34)
+ * (ABI 16, added) -----------------------------------------------------------------------
+ * Segment s in [0, n_seg) is the slots t in [ptr[s], ptr[s + 1]) (ptr: int32, n_seg + 1,
+ * ascending, ptr[n_seg] <= n_slots; a CSR rowptr or a CSC colptr).  A slot's value is
+ * x_t = vals[(eid ? eid[t] : t) * ld + off] (fp32; vals has n_vals rows of pitch ld, so
+ * ld / off pick one head of an (E, H) attention export and eid = csc_eid reads it in column
+ * order; an eid outside [0, n_vals) reads as NaN), its id is ids ? ids[t] : t - ptr[s]
+ * (int32, >= 0: col on the row side, csc_row on the column side).
+ *
+ * Order: msha_topk_inner's -- value descending, then id ascending; -0.0 folded onto +0.0,
+ * +inf first, every NaN below -inf and all NaNs equal.  Integer compares and adds, ordinary
+ * stores, no atomics: the results are unique, bitwise repeatable and independent of the
+ * grid and of `chunk`.
+ *
+ * msha_segment_ties (Explainer.py:25-30, "argwhere(row == max(row))"):
+ *   max_val (fp32, n_seg)    the segment's maximum (-inf for an empty segment, +0.0 for a
+ *                            zero of either sign, a NaN when every slot is NaN)
+ *   n_tie   (int32, n_seg)   the slots with x_t >= thr, thr = max - rtol * |max| formed once
+ *                            per segment in fp32 (product and difference each rounded); with
+ *                            rtol = 0 or a non-finite maximum: the slots whose image equals
+ *                            the maximum's
+ *   tie_ptr (int32, n_seg + 1)  the exclusive scan of n_tie, made on the device
+ *   tie_idx (int32, n_slots) those slots' ids at tie_ptr[s] .. tie_ptr[s + 1], in slot
+ *                            order; the rest of the buffer is left as it was.  Sized at the
+ *                            number of slots, so no count is read back.
+ *   0 <= rtol < 1.
+ * msha_segment_topk (Explainer.py:31-34): out_val / out_idx (n_seg, k) fp32 / int64, each
+ *   segment's k best, best first; slots past the segment's length hold -inf and -1, as in
+ *   msha_topk_inner.  1 <= k <= 128: the k of 200 in the reference's commented-out variant
+ *   is out of range and returns MSHA_ERR_ARG.
+ *
+ * Two regimes, chosen per segment on the device: a segment of at most W slots (W the power
+ * of two in [4, 64] at or above twice the mean length n_slots / n_seg) is handled by a
+ * group of W lanes; a longer one is cut into chunks of at most `chunk` slots (in
+ * [64, 4096]; 0: 256 in tie mode, for top-K the power of two in [256, 4096] at or above
+ * sqrt(n_slots / n_seg * k)), one wave per (segment, chunk), found through a scan of the
+ * segments' chunk counts, and the chunks' partial results are combined in chunk order.
+ *
+ * Stateless; every buffer is the caller's.  ws: msha_segment_select_workspace_size bytes
+ * (k = 0: tie mode), 16-byte aligned, contents irrelevant.  n_seg, n_slots < 2^31 - 1;
+ * n_seg = 0 launches nothing. */
+MSHA_API size_t msha_segment_select_workspace_size(int64_t n_seg, int64_t n_slots, int32_t k,
+                                                   int32_t chunk); /* (ABI 16, added) */
+MSHA_API int msha_segment_ties(int64_t n_seg, int64_t n_slots, const int32_t* ptr,
+                               const float* vals, int64_t n_vals, int64_t ld, int64_t off,
+                               const int32_t* eid, const int32_t* ids, float rtol,
+                               int32_t chunk, float* max_val, int32_t* n_tie, int32_t* tie_ptr,
+                               int32_t* tie_idx, void* ws, size_t ws_bytes,
+                               msha_stream_t stream); /* (ABI 16, added) */
+MSHA_API int msha_segment_topk(int64_t n_seg, int64_t n_slots, const int32_t* ptr,
+                               const float* vals, int64_t n_vals, int64_t ld, int64_t off,
+                               const int32_t* eid, const int32_t* ids, int32_t k, int32_t chunk,
+                               float* out_val, int64_t* out_idx, void* ws, size_t ws_bytes,
+                               msha_stream_t stream); /* (ABI 16, added) */
+
 /* ---- Filtered link ranks, MRR and Hits@K for the inner-product scorer (LLP.py:20, the
  * ranking protocol around it) (ABI 16, added) ------------------------------------------
  * For query position b in [0, n_q) with target candidate t = target[b] (a GLOBAL row; it

@@ -220,6 +220,12 @@ SIGNATURES = {
                                   I32, I32, P, P, P, P, SZ, P]),
     "msha_topk_merge_workspace_size": (SZ, [I64, I64, I64, I32]),
     "msha_topk_merge": (C.c_int, [I64, I64, I64, I32, P, P, I32, P, P, P, SZ, P]),
+    # select over ragged segments: the attention explanation (ABI 16, added)
+    "msha_segment_select_workspace_size": (SZ, [I64, I64, I32, I32]),
+    "msha_segment_ties": (C.c_int, [I64, I64, P, P, I64, I64, I64, P, P, F32, I32, P, P, P, P, P,
+                                    SZ, P]),
+    "msha_segment_topk": (C.c_int, [I64, I64, P, P, I64, I64, I64, P, P, I32, I32, P, P, P, SZ,
+                                    P]),
     # filtered link ranks (ABI 16, added)
     "msha_rank_inner_supported": (C.c_int, [I32, I32]),
     "msha_rank_inner_splits": (C.c_int, [I64, I64, I32, I32]),

@@ -1277,6 +1277,116 @@ def topk_merge(vals, idx=None, k=1, sigmoid=False):
     return out_v, out_i
 
 
+# ----------------------------------------------------- select over ragged segments ---
+class Ragged:
+    """Ragged lists on the device: list s is ``idx[ptr[s]:ptr[s + 1]]`` (int32 both).
+    ``segment_ties`` also leaves the segment maxima in ``max_val`` and the list lengths in
+    ``count``.  ``idx`` is sized for the worst case; only ``idx[:ptr[-1]]`` is meaningful."""
+
+    __slots__ = ("ptr", "idx", "max_val", "count")
+
+    def __init__(self, ptr, idx, max_val=None, count=None):
+        self.ptr, self.idx, self.max_val, self.count = ptr, idx, max_val, count
+
+    def __iter__(self):  # ptr, idx = ragged
+        return iter((self.ptr, self.idx))
+
+    def lists(self):
+        """The lists as numpy arrays on the host (one copy of ptr and idx: a sync)."""
+        ptr = self.ptr.cpu().numpy()
+        idx = self.idx[: int(ptr[-1])].cpu().numpy()
+        return [idx[ptr[s]:ptr[s + 1]] for s in range(len(ptr) - 1)]
+
+
+def _segment_args(name, ptr, vals, ids, eid, col, chunk):
+    """The shared arguments of ``segment_ties`` / ``segment_topk`` for the library."""
+    for t, what in ((ptr, "ptr"), (ids, "ids"), (eid, "eid")):
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
+            raise TypeError(f"{name}: {what} must be a contiguous 1-D int32 tensor")
+    if ptr.numel() < 1:
+        raise ValueError(f"{name}: ptr needs n_seg + 1 entries")
+    if vals.dtype != torch.float32 or vals.dim() not in (1, 2):
+        raise TypeError(f"{name}: vals must be float32, (n,) or (n, H) with col=")
+    vals = vals.detach()
+    if vals.dim() == 2:
+        if col is None or not 0 <= int(col) < vals.shape[1]:
+            raise ValueError(f"{name}: a 2-D vals needs col in [0, {vals.shape[1]})")
+        if vals.shape[0] > 1 and (vals.stride(1) != 1 or vals.stride(0) < vals.shape[1]):
+            vals = vals.contiguous()
+        ld, off = (vals.stride(0) if vals.shape[0] > 1 else vals.shape[1]), int(col)
+    else:
+        if col is not None:
+            raise ValueError(f"{name}: col goes with a 2-D vals")
+        if vals.numel() > 1 and vals.stride(0) < 1:
+            vals = vals.contiguous()
+        ld, off = (vals.stride(0) if vals.numel() > 1 else 1), 0
+    n_vals = vals.shape[0]
+    n_slots = eid.numel() if eid is not None else (ids.numel() if ids is not None else n_vals)
+    if ids is not None and ids.numel() != n_slots:
+        raise ValueError(f"{name}: ids and eid must have one entry per slot")
+    if eid is None and n_vals < n_slots:
+        raise ValueError(f"{name}: vals needs one row per slot")
+    chunk = 0 if chunk is None else int(chunk)
+    if chunk != 0 and not 64 <= chunk <= 4096:
+        raise ValueError(f"{name}: chunk must be in [64, 4096], got {chunk}")
+    _lib.require_cuda(ptr, vals, ids, eid)
+    return vals, n_vals, ld, off, n_slots, chunk
+
+
+def segment_ties(ptr, vals, ids=None, eid=None, col=None, rtol: float = 0.0, chunk=None):
+    """For each segment ``[ptr[s], ptr[s + 1])`` of slots the maximum and the slots that
+    attain it (Explainer.py:25-30 over a CSR row or a CSC column, without the dense
+    matrix): a ``Ragged`` whose list s holds the ids of the slots with
+    ``value >= max - rtol * |max|`` in slot order (``rtol=0`` or a non-finite maximum:
+    equal to the maximum under ``topk_inner``'s order: -0.0 == +0.0, all NaNs equal and
+    below -inf), with ``max_val`` (-inf for an empty segment) and ``count``.
+
+    A slot's value is ``vals[e]`` (``vals`` 1-D, any stride: a head of the attention
+    export as ``attd[:, h]``) or ``vals[e, col]``, with ``e = eid[t]`` (``eid`` None: the
+    slot itself); its id is ``ids[t]`` (None: the position in its segment).  ``ptr``,
+    ``ids``, ``eid``: int32.  ``chunk``: slots per wave of a long segment (None: the
+    library's choice); the result does not depend on it.  Inference only; no host sync (the lists are sized for
+    the worst case), so the call can be captured into a HIP graph."""
+    vals, n_vals, ld, off, n_slots, chunk = _segment_args("segment_ties", ptr, vals, ids, eid,
+                                                          col, chunk)
+    rtol = float(rtol)
+    if not 0.0 <= rtol < 1.0:
+        raise ValueError(f"segment_ties: rtol must be in [0, 1), got {rtol}")
+    n_seg = ptr.numel() - 1
+    dev = ptr.device
+    max_val = torch.empty(n_seg, dtype=torch.float32, device=dev)
+    count = torch.empty(n_seg, dtype=torch.int32, device=dev)
+    tie_ptr = torch.zeros(n_seg + 1, dtype=torch.int32, device=dev)
+    tie_idx = torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev)
+    ws = _workspace(dev, _lib.fn("msha_segment_select_workspace_size")(n_seg, n_slots, 0, chunk))
+    _lib.call("msha_segment_ties", n_seg, n_slots, ptr.data_ptr(),
+              vals.data_ptr() if n_vals else None, n_vals, ld, off, _lib.ptr(eid), _lib.ptr(ids),
+              rtol, chunk, max_val.data_ptr(), count.data_ptr(), tie_ptr.data_ptr(),
+              tie_idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream(ptr))
+    return Ragged(tie_ptr, tie_idx, max_val, count)
+
+
+def segment_topk(ptr, vals, k, ids=None, eid=None, col=None, chunk=None):
+    """The ``k`` best slots of each segment under ``topk_inner``'s order (value
+    descending, then id ascending; Explainer.py:31-34): ``(values, indices)``,
+    (n_seg, k) float32 / int64, best first, -inf / -1 past a segment's length.
+    1 <= k <= 128 (the 200 of the reference's commented-out variant is out of range).
+    Arguments, ``chunk`` and capture as ``segment_ties``."""
+    k = _topk_k(k)
+    vals, n_vals, ld, off, n_slots, chunk = _segment_args("segment_topk", ptr, vals, ids, eid,
+                                                          col, chunk)
+    n_seg = ptr.numel() - 1
+    dev = ptr.device
+    out_v = torch.empty(n_seg, k, dtype=torch.float32, device=dev)
+    out_i = torch.empty(n_seg, k, dtype=torch.int64, device=dev)
+    ws = _workspace(dev, _lib.fn("msha_segment_select_workspace_size")(n_seg, n_slots, k, chunk))
+    _lib.call("msha_segment_topk", n_seg, n_slots, ptr.data_ptr(),
+              vals.data_ptr() if n_vals else None, n_vals, ld, off, _lib.ptr(eid), _lib.ptr(ids),
+              k, chunk, out_v.data_ptr(), out_i.data_ptr(), ws.data_ptr(), ws.numel(),
+              _stream(ptr))
+    return out_v, out_i
+
+
 # ------------------------------------------------------------ filtered link ranks ---
 def rank_inner(q, table, target, rows=None, exclude=None, col_offset=0, target_logit=None,
                splits=None, check=True):

@@ -469,6 +469,18 @@ def _attention_uv(heads, s_input, r_input, graph: Graph, city_adj, province_adj,
                   source_index, training, record=False, Coeff12=None, Coeff3=None,
                   Coeff4=None, packed=False):
     """OursLayer inter + intra attention of all heads: (u (N, H, F), v (M, H, F))."""
+    u, v, attd, bstat, groups, src = _attention_aux(heads, s_input, r_input, graph, city_adj,
+                                                    province_adj, source_index, training,
+                                                    packed)
+    if record:
+        _record(attd, bstat, graph, groups, src, heads, Coeff12, Coeff3, Coeff4)
+    return u, v
+
+
+def _attention_aux(heads, s_input, r_input, graph: Graph, city_adj, province_adj, source_index,
+                   training, packed=False):
+    """``_attention_uv`` with what record mode and ``explain.attention_record`` read:
+    (u, v, attd (E, H), bstat (B, H, 8), groups, src)."""
     H = len(heads)
     Fd = heads[0].out_features
     n, m = s_input.shape[0], r_input.shape[0]
@@ -495,9 +507,7 @@ def _attention_uv(heads, s_input, r_input, graph: Graph, city_adj, province_adj,
     u, v, attd, bstat = MF.ours_attention(graph, groups, src, el, er, h1.view(m, H, Fd),
                                           h2.view(n, H, Fd), a3s, a4s, p=heads[0].dropout,
                                           training=training, return_aux=True)
-    if record:
-        _record(attd, bstat, graph, groups, src, heads, Coeff12, Coeff3, Coeff4)
-    return u, v
+    return u, v, attd, bstat, groups, src
 
 
 class _RecordState:
