@@ -281,9 +281,9 @@ MSHA_API int32_t msha_ours_pack_draws(int32_t mode);
 /* (ABI 15) The fp32 weight gradient's kernel (projection backward, dW = X^T D'): mode 0 =
  * auto (default: from 131,072 rows -- MSHA_WGRAD_S3_MIN_ROWS -- the operands split into
  * three bf16 terms in registers, six products on the bf16 MFMA; the exact-fp32 MFMA below),
- * 1 = exact-fp32 MFMA, 2 = split-bf16 through LDS images, 3 = the register split at any
- * size (MSHA_WGRAD=fp32 / x3 / s3 start the process with 1 / 2 / 3).  Returns the previous
- * mode; mode < 0 only queries. */
+ * 1 = exact-fp32 MFMA, 3 = the register split at any size (MSHA_WGRAD=fp32 / s3 start the
+ * process with 1 / 3; any other word is ignored).  Returns the previous mode; any other
+ * value of mode (negative, 2 -- a removed kernel's number --, above 3) only queries. */
 MSHA_API int32_t msha_wgrad_kernel(int32_t mode);
 
 /* Column-side (transposed) aggregate over the CSC view:

@@ -19,7 +19,7 @@ struct BipReduce {
   void* out_t;
   float* out_f;
   int32_t nb, stride, n, n_t;
-  int32_t seg, seg_stride, blk, blk_off, fblk, fstride;
+  int32_t fblk;  // entries of the fp32 tail (n - n_t in every caller; 1 where there is none)
   int32_t bf16;
   int32_t blocks() const { return (n + 15) / 16; }
 };
@@ -49,13 +49,10 @@ __device__ __forceinline__ void bip_reduce_block(const BipReduce& r, int blk_id,
     float sum = red[0][c];
 #pragma unroll 8
     for (int q = 1; q < 64; ++q) sum += red[q][c];
-    // (a head-split launch's partials are [head blk][column seg]: entry i lands at column
-    // (i % blk) / seg, head i / blk of the HT-head table)
     if (i < r.n_t)
-      reinterpret_cast<T*>(r.out_t)[((i % r.blk) / r.seg) * r.seg_stride + (i / r.blk) * r.blk_off +
-                                    i % r.seg] = from_f32<T>(sum);
+      reinterpret_cast<T*>(r.out_t)[i] = from_f32<T>(sum);
     else
-      r.out_f[((i - r.n_t) % r.fblk) * r.fstride + (i - r.n_t) / r.fblk] = sum;
+      r.out_f[(i - r.n_t) % r.fblk + (i - r.n_t) / r.fblk] = sum;
   }
 }
 

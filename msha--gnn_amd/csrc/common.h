@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <string>
 
@@ -24,6 +25,14 @@ int check_launch(const char* what);
   do {                                                        \
     if (!(cond)) return ::msha::fail(MSHA_ERR_ARG, (msg));    \
   } while (0)
+
+// ---- run-time knobs (INTEGRATION.md lists them) ----
+// Integer knob from the environment; unset or empty gives def.  Not cached: a call site
+// that reads once per process keeps the result in a static.
+inline int64_t env_int(const char* name, int64_t def) {
+  const char* v = getenv(name);
+  return v != nullptr && *v ? (int64_t)strtoll(v, nullptr, 10) : def;
+}
 
 // ---- wave helpers ----
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }

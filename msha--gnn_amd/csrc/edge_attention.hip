@@ -1284,12 +1284,6 @@ static bool shape_supported(int H, int F) {
   return false;
 }
 
-// integer tuning knob from the environment (A/B measurements; default = shipped choice)
-static int env_int(const char* name, int def) {
-  const char* v = getenv(name);
-  return v != nullptr && *v ? atoi(v) : def;
-}
-
 // one wave per row (or chunk), 4 waves per block; grid-stride beyond the cap
 static dim3 wave_grid(int64_t items) { return dim3(grid_for(items, 4, 1 << 20)); }
 
@@ -1592,8 +1586,7 @@ static void launch_bwd_fused(const msha_graph* g, int heads, int feat, const flo
   const bool slot_de = g->csr_slot != nullptr && g->n_edges * 4 * (int64_t)heads >= DE_SLOT_MIN_BYTES;
   // MSHA_COLS_NOBUF=1 forces the pointer-load column pass (what tables of 2 GiB or more
   // take) so tests cover it at small sizes; read per call, so a test can flip it
-  const char* nobuf = getenv("MSHA_COLS_NOBUF");
-  const bool buf_ok = !(nobuf != nullptr && *nobuf == '1') &&
+  const bool buf_ok = env_int("MSHA_COLS_NOBUF", 0) != 1 &&
                       g->n_rows * (int64_t)heads * feat * (int64_t)sizeof(T) < lim &&
                       g->n_edges * 4 * (int64_t)heads < lim && g->n_rows * 4 * rec_stride(heads) < lim;
 #define X(h, f)                                                                                \

@@ -572,11 +572,8 @@ __global__ void __launch_bounds__(kWavesB * 64) bip2_bwd_kernel(
 }  // namespace bip2
 
 bool bip2_ok(const msha_graph* g, int heads, int feat, float slope) {
-  static const int env = [] {
-    const char* v = getenv("MSHA_BIP2");
-    return v != nullptr && *v ? atoi(v) : 1;
-  }();
-  return env != 0 && heads == 2 && feat == 64 && g->rowmask != nullptr && g->n_cols <= 32 &&
+  static const bool env = env_int("MSHA_BIP2", 1) != 0;
+  return env && heads == 2 && feat == 64 && g->rowmask != nullptr && g->n_cols <= 32 &&
          slope >= 0.f && slope <= 1.f && g->n_rows * (int64_t)bip2::kD * 4 < (1ll << 31) &&
          g->n_edges * 8ll < (1ll << 31);
 }

@@ -1138,11 +1138,8 @@ __global__ void __launch_bounds__(kWaves * 64) bip3_bwd_kernel(
 }  // namespace bip3
 
 bool bip3_enabled() {
-  static const int env = [] {
-    const char* v = getenv("MSHA_BIP3");
-    return v != nullptr && *v ? atoi(v) : 1;
-  }();
-  return env != 0;
+  static const bool env = env_int("MSHA_BIP3", 1) != 0;
+  return env;
 }
 
 // 1 = launched (forward + the v reduce); the caller checked bip2_ok (2 x 64, M <= 32,
@@ -1195,8 +1192,7 @@ int bip3_bwd(const msha_graph* g, int dtype, const float* el, const float* er, c
   // outstanding load).  Its dropout variants still spill (the keep words): with dropout the
   // mask kernel runs.  MSHA_BIP3_BWD32 (read per call): 1 forces this kernel, 0 the mask one.
   if (dtype != MSHA_DTYPE_BF16) {
-    const char* v = getenv("MSHA_BIP3_BWD32");
-    const int force = v != nullptr && *v ? atoi(v) : -1;
+    const int force = (int)env_int("MSHA_BIP3_BWD32", -1);
     if (force == 0 || (force < 0 && dp.active)) return 0;
   }
   const int32_t n_tiles = (int32_t)((g->n_rows + bip3::kTile - 1) / bip3::kTile);

@@ -956,10 +956,7 @@ using namespace msha;
 // the intra-dropout draw form of ours_fwd_lds_kernel: packed (default; MSHA_OURS_PACK_DRAWS=0
 // starts the process with the per-node form), switchable for A/B runs and the bitwise test
 static std::atomic<int>& ours_pack_flag() {
-  static std::atomic<int> f([] {
-    const char* v = getenv("MSHA_OURS_PACK_DRAWS");
-    return v == nullptr || atoi(v) != 0 ? 1 : 0;
-  }());
+  static std::atomic<int> f(env_int("MSHA_OURS_PACK_DRAWS", 1) != 0 ? 1 : 0);
   return f;
 }
 

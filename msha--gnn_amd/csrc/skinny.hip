@@ -730,201 +730,38 @@ __global__ void __launch_bounds__(64 * kProjWaves) pair_kernel(
   }
 }
 
-// The fp32 pair scorer with ONE register set of rows (pair_kernel holds two: the tile in
-// use and the next one, 128 VGPRs of rows at K = 128, which left it at 2 waves per SIMD
-// with a spill).  A lane's row registers ci[i] / cj[i] feed steps [i SPL, (i + 1) SPL);
-// once those MFMAs have issued, slot i is reloaded with the NEXT tile's rows, so the next
-// tile's gathers are in flight under the rest of this tile (7/8 of a tile of lead for the
-// first slot).  The next tile's pair indices are loaded a whole tile earlier still.
+// ------------------------------------------- fp32 pair scorer on split bf16 MFMA ---
+// The fp32 pair scorer for tables inside a buffer window (msha_pair_linear's table_rows:
+// rows x ldg x 4 < 4 GiB; everything else takes pair_kernel).  The fp32 products are
+// computed on the bf16 matrix pipe (16x the fp32 MFMA rate): every fp32 operand is split
+// into three bf16 terms, x = x_h + x_m + x_l (x_h = bf16(x), x_m = bf16(x - x_h), x_l =
+// bf16(x - x_h - x_m); both subtractions exact in fp32, |x - sum| <= 2^-27 |x|), and each
+// k-chunk runs the six products whose weight reaches fp32's 2^-24: hh, hm, mh, mm, hl, lh
+// (the dropped ml, lm, ll are <= 2^-26 |x w| each).  Each bf16 x bf16 product is exact in
+// fp32 and the MFMA accumulates in fp32, so a score carries fp32-level error (the same
+// order as the exact-fp32 MFMA's; tests/test_gpu_kernels.py holds this kernel and
+// pair_kernel to 1e-5 of fp64).  Cost per 32-wide k-chunk and 16 x 16 block: 6 x 16 cycles
+// on the bf16 pipe against 8 x 32 cycles of v_mfma_f32_16x16x4_f32.  The hadamard x_i * x_j
+// is rounded to fp32 first (the reference's fp32 product), then split.  W is split once
+// into three bf16 [n][k] images (3 x 34 KB at K = N = 128), the only LDS: no staging
+// tile, so WPS waves per SIMD fit.
+//   A wave holds ONE register set of rows.  Rows are line-major: step s of lane group g
+// reads columns [32 s + 8 g, +8) -- 32 contiguous bytes, a full 128-byte line per row per
+// step -- and both of a step's slots are reloaded with the NEXT tile's rows right after
+// that step's products are formed, so the next tile's gathers are in flight under the
+// rest of this tile.  The next tile's pair indices are loaded a whole tile earlier still.
 //   The waits must stay exact for that lead to exist, which decides the memory ops:
 //   - row gathers are buffer loads at 32-bit offsets from the table base (plain 64-bit
 //     loads let the register allocator rotate the row registers through copies at the
-//     loop latch, each copy waiting on its load);
+//     loop latch, each copy waiting on its load); the descriptors end at the tables'
+//     ends, so an index past them reads zeros instead of faulting;
 //   - the epilogue writes the MFMA C layout (row 4 g + i, column 16 c + r16) with
 //     buffer stores through a per-tile descriptor that ends at the batch's last row, so
 //     rows past it drop without a branch: every tile issues the same count of stores
 //     and the compiler's vmcnt at the next tile's first use counts them (a branch
-//     around the stores made it assume none and wait for every reload);
-//   - no staging tile: the LDS holds W alone, so WPS waves per SIMD fit.
-//   - line-major k: slot i of lane group g holds columns [16 i + 4 g, +4), so one load
-//     instruction reads 64 contiguous bytes of each of its 16 rows and slots 2j, 2j + 1
-//     (reloaded together) cover one 128-byte line.  (pair_kernel's k = g K/4 + s puts a
-//     lane group's 16 bytes of a slot in a different line for each g: reloaded a slot at
-//     a time, every line came from L2 eight times.)  The W image rows follow the same
-//     k order.
-// The host picks this kernel when both tables fit a buffer window (msha_pair_linear's
-// table_rows: rows x ldg x 4 < 4 GiB); the descriptors end at the tables' ends, so an
-// index past them reads zeros instead of faulting.  Same activation bits and dropout
-// keys (p * N + n) as pair_kernel; the k order differs, so the sums round differently.
-#ifndef PAIR32_WPS
-#define PAIR32_WPS 3
-#endif
-template <int K, int N, int WPS>
-__global__ void __launch_bounds__(256 * WPS) pair_roll_kernel(
-    int M, const float* __restrict__ G, int64_t ldg, const int64_t* __restrict__ gi,
-    const float* __restrict__ G2, int64_t ldg2, const int64_t* __restrict__ gj,
-    const float* __restrict__ Wlin, const float* __restrict__ bias, int act, Dropout dp,
-    float* __restrict__ out, uint32_t bytes_a, uint32_t bytes_b) {
-  using Gm = ProjGeo<float, K, N>;
-  constexpr int kWaves = 4 * WPS;
-  constexpr int SPL = Gm::S / Gm::NLD;  // MFMA steps fed by one 16-byte row register
-  __shared__ __attribute__((aligned(16))) float Wl[Gm::WBYTES / 4];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = lane >> 4, r16 = lane & 15;
-
-  {  // B[k][n] = Wlin[n][k] -> image row 4 s + g for k = 16 (s / 4) + 4 g + s % 4
-    WPieces<K, N, 64 * kWaves> p;
-    p.load(Wlin, tid);
-#pragma unroll
-    for (int i = 0; i < p.IT; ++i) {
-      const int idx = tid + 64 * kWaves * i;
-      if (p.ok(idx)) {
-        const int n = idx / (K / 4), k4 = idx % (K / 4);
-        const uint32_t e[4] = {p.v[i].x, p.v[i].y, p.v[i].z, p.v[i].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int k = 4 * k4 + j;
-          const int row = 4 * (4 * (k / 16) + k % 4) + (k % 16) / 4;
-          Wl[row * Gm::PW + n] = __uint_as_float(e[j]);
-        }
-      }
-    }
-  }
-  __syncthreads();
-
-  float bv[Gm::NB];
-#pragma unroll
-  for (int c = 0; c < Gm::NB; ++c) bv[c] = (act & SK_BIAS) ? bias[c * 16 + r16] : 0.f;
-  const uint64_t doff = (act & SK_DROPOUT) ? dropout_offset(dp, dp.offset) : 0;
-
-  const int nblk = gridDim.x;
-  const int gw = (w >> 2) * (nblk * 4) + blockIdx.x * 4 + (w & 3);
-  const int nw = nblk * kWaves;
-  const int tiles = (M + 15) / 16;
-  if (gw >= tiles) return;
-
-  // the tables (G / G2 are non-null: checked on the host; make_rsrc's null test would put
-  // the descriptor in VGPRs and waterfall every load)
-  const rsrc_t r_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G), 0, bytes_a, 0x00020000);
-  const rsrc_t r_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G2), 0, bytes_b, 0x00020000);
-  // rows past the batch (and tiles past the last) clamp to the last pair: valid
-  // addresses, never stored, so every reload is unconditional
-  auto load_idx = [&](int t, int64_t& a, int64_t& b) {
-    const int row = min(t * 16 + r16, M - 1);
-    a = gi[row];
-    b = gj[row];
-  };
-  // byte offsets of this lane's first 4 columns of the two rows (< 4 GiB: the host's check).
-  // An index outside [0, rows) maps past the window (reads zeros); the test also keeps
-  // the index's high word live, so the register allocator does not put the offset into
-  // the dead high half of the NEXT index load's destination (a write that would wait on
-  // that load: vmcnt(0) at every tile start)
-  // (the row counts behind the windows: an index at or past them, or negative, reads
-  // zeros instead of wrapping its byte offset past 4 GiB back into the table)
-  const uint64_t rows_a = ((uint64_t)bytes_a - 4 * K) / (4 * (uint64_t)ldg) + 1;
-  const uint64_t rows_b = ((uint64_t)bytes_b - 4 * K) / (4 * (uint64_t)ldg2) + 1;
-  auto offset_a = [&](int64_t a) -> uint32_t {
-    return (uint64_t)a >= rows_a ? 0xFFFFFFF0u : (uint32_t)((a * ldg + 4 * g) * 4);
-  };
-  auto offset_b = [&](int64_t b) -> uint32_t {
-    return (uint64_t)b >= rows_b ? 0xFFFFFFF0u : (uint32_t)((b * ldg2 + 4 * g) * 4);
-  };
-  auto mfma_tile = [&](int t, u32x4_t* ci, u32x4_t* cj, uint32_t na, uint32_t nb) {
-    f32x4 acc[Gm::NB];
-#pragma unroll
-    for (int c = 0; c < Gm::NB; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* Wf = Wl + g * Gm::PW + r16;
-    float bc[Gm::NB], bn[Gm::NB];
-#pragma unroll
-    for (int c = 0; c < Gm::NB; ++c) bc[c] = Wf[c * 16];
-#pragma unroll
-    for (int s = 0; s < Gm::S; ++s) {
-      if (s + 1 < Gm::S) {
-#pragma unroll
-        for (int c = 0; c < Gm::NB; ++c) bn[c] = Wf[4 * (s + 1) * Gm::PW + c * 16];
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      const float a = __uint_as_float(ci[s / 4][s % 4]) * __uint_as_float(cj[s / 4][s % 4]);
-#pragma unroll
-      for (int c = 0; c < Gm::NB; ++c)
-        acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bc[c], acc[c], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if ((s + 1) % (2 * SPL) == 0) {  // the two slots of one 128-byte line
-        const int i = s / SPL - 1;
-        ci[i] = buf_b128(r_a, na + 64u * i);
-        ci[i + 1] = buf_b128(r_a, na + 64u * (i + 1));
-        cj[i] = buf_b128(r_b, nb + 64u * i);
-        cj[i + 1] = buf_b128(r_b, nb + 64u * (i + 1));
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int c = 0; c < Gm::NB; ++c) bc[c] = bn[c];
-    }
-    // ---- epilogue on the C layout: element (row t 16 + 4 g + i, column 16 c + r16)
-    const int rows = min(16, M - t * 16);
-    const rsrc_t r_o = make_rsrc(out + (int64_t)t * 16 * N, (uint32_t)(rows * N * 4));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = t * 16 + 4 * g + i;
-#pragma unroll
-      for (int c = 0; c < Gm::NB; ++c) {
-        float x = acc[c][i] + bv[c];
-        if (act & SK_RELU) x = fmaxf(x, 0.f);
-        if (act & SK_DROPOUT)
-          x *= philox_x(dp.seed, doff, (uint64_t)row * N + c * 16 + r16) >= dp.threshold
-                   ? dp.scale
-                   : 0.f;
-        if (act & SK_SIGMOID) x = 1.f / (1.f + __expf(-x));
-        buf_store_f32(r_o, (uint32_t)(((4 * g + i) * N + c * 16 + r16) * 4), x);
-      }
-    }
-  };
-
-  u32x4_t ci[Gm::NLD], cj[Gm::NLD];
-  int64_t xa, xb;
-  load_idx(gw, xa, xb);
-  {
-    const uint32_t oa = offset_a(xa), ob = offset_b(xb);
-    // in slot order, as the loop reloads them: the wait counts at the loop head merge
-    // this path's (a reordered prologue let slot 0 look like one of the last loads and
-    // the loop then waited for nearly every reload at each tile start)
-#pragma unroll
-    for (int i = 0; i < Gm::NLD; i += 2) {
-      ci[i] = buf_b128(r_a, oa + 64u * i);
-      ci[i + 1] = buf_b128(r_a, oa + 64u * (i + 1));
-      cj[i] = buf_b128(r_b, ob + 64u * i);
-      cj[i + 1] = buf_b128(r_b, ob + 64u * (i + 1));
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  load_idx(gw + nw, xa, xb);
-  for (int t = gw; t < tiles; t += nw) {
-    // the next tile's row offsets (its indices were loaded one tile ago), then the
-    // indices of the tile after it
-    const uint32_t oa = offset_a(xa), ob = offset_b(xb);
-    load_idx(t + 2 * nw, xa, xb);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_tile(t, ci, cj, oa, ob);
-  }
-}
-
-// ------------------------------------------- fp32 pair scorer on split bf16 MFMA ---
-// The same resident-W rolling-row structure with the fp32 products computed on the bf16
-// matrix pipe (16x the fp32 MFMA rate): every fp32 operand is split into three bf16
-// terms, x = x_h + x_m + x_l (x_h = bf16(x), x_m = bf16(x - x_h), x_l = bf16(x - x_h -
-// x_m); both subtractions exact in fp32, |x - sum| <= 2^-27 |x|), and each k-chunk runs
-// the six products whose weight reaches fp32's 2^-24: hh, hm, mh, mm, hl, lh (the dropped
-// ml, lm, ll are <= 2^-26 |x w| each).  Each bf16 x bf16 product is exact in fp32 and the
-// MFMA accumulates in fp32, so a score carries fp32-level error (the same order as the
-// exact-fp32 MFMA's; tests/test_gpu_kernels.py holds both kernels to 1e-5 of fp64).
-// Cost per 32-wide k-chunk and 16 x 16 block: 6 x 16 cycles on the bf16 pipe against
-// 8 x 32 cycles of v_mfma_f32_16x16x4_f32.  The hadamard x_i * x_j is rounded to fp32
-// first (the reference's fp32 product), then split.  W is split once into three bf16
-// [n][k] images (3 x 34 KB at K = N = 128).  Rows: line-major, step s of lane group g
-// reads columns [32 s + 8 g, +8) -- 32 contiguous bytes, a full 128-byte line per row
-// per step -- and both of a step's slots are reloaded with the next tile's rows right
-// after that step's MFMAs.
+//     around the stores made it assume none and wait for every reload).
+// Same activation bits and dropout keys (p * N + n) as pair_kernel; the k order differs,
+// so the sums round differently.
 #ifndef PAIR_X3_WPS
 #define PAIR_X3_WPS 3
 #endif
@@ -985,16 +822,23 @@ __global__ void __launch_bounds__(256 * WPS) pair_x3_kernel(
   const int tiles = (M + 15) / 16;
   if (gw >= tiles) return;
 
-  // (G / G2 non-null, host-checked: a null test would put the descriptors in VGPRs)
+  // the tables (G / G2 are non-null: checked on the host; make_rsrc's null test would put
+  // the descriptors in VGPRs and waterfall every load)
   const rsrc_t r_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G), 0, bytes_a, 0x00020000);
   const rsrc_t r_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G2), 0, bytes_b, 0x00020000);
+  // rows past the batch (and tiles past the last) clamp to the last pair: valid
+  // addresses, never stored, so every reload is unconditional
   auto load_idx = [&](int t, int64_t& a, int64_t& b) {
     const int row = min(t * 16 + r16, M - 1);
     a = gi[row];
     b = gj[row];
   };
-  // this lane's first 8 columns of each row (index outside [0, rows): past the window;
-  // the test keeps the index's high word live, see pair_roll_kernel)
+  // byte offsets of this lane's first 8 columns of the two rows (< 4 GiB: the host's
+  // check).  An index at or past the row count behind the window, or negative, maps past
+  // the window (reads zeros) instead of wrapping its byte offset past 4 GiB back into the
+  // table; the test also keeps the index's high word live, so the register allocator does
+  // not put the offset into the dead high half of the NEXT index load's destination (a
+  // write that would wait on that load: vmcnt(0) at every tile start)
   const uint64_t rows_a = ((uint64_t)bytes_a - 4 * K) / (4 * (uint64_t)ldg) + 1;
   const uint64_t rows_b = ((uint64_t)bytes_b - 4 * K) / (4 * (uint64_t)ldg2) + 1;
   auto offset_a = [&](int64_t a) -> uint32_t {
@@ -1078,6 +922,9 @@ __global__ void __launch_bounds__(256 * WPS) pair_x3_kernel(
   load_idx(gw, xa, xb);
   {
     const uint32_t oa = offset_a(xa), ob = offset_b(xb);
+    // in slot order, as the loop reloads them: the wait counts at the loop head merge
+    // this path's (a reordered prologue let slot 0 look like one of the last loads and
+    // the loop then waited for nearly every reload at each tile start)
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       ci[i] = buf_b128(r_a, oa + slot_off(i));
@@ -1087,6 +934,8 @@ __global__ void __launch_bounds__(256 * WPS) pair_x3_kernel(
   }
   load_idx(gw + nw, xa, xb);
   for (int t = gw; t < tiles; t += nw) {
+    // the next tile's row offsets (its indices were loaded one tile ago), then the
+    // indices of the tile after it
     const uint32_t oa = offset_a(xa), ob = offset_b(xb);
     load_idx(t + 2 * nw, xa, xb);
     __builtin_amdgcn_sched_barrier(0);
@@ -1663,7 +1512,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
 // three bf16 terms x = x_h + x_m + x_l (|x - sum| <= 2^-27 |x|) and the six products whose
 // weight reaches fp32's 2^-24 (lh, hl, mm, mh, hm, hh, small first) run as
 // v_mfma_f32_32x32x16_bf16: 16x the exact-fp32 MFMA's rate, so the six cost 3/8 of one
-// exact product.  Unlike wgrad_x3.hip (both operands staged as bf16 LDS images and read
+// exact product.  Unlike a form with both operands staged as bf16 LDS images and read
 // back with transposed LDS reads, one block of six 18 KB images per CU) no operand is
 // transposed: a 16-row step's k index is (row group q = lane >> 5, j < 8), so lane
 // (i = lane & 31, q) loads float4 X[r + 8q + j][4i .. 4i + 3] and D[r + 8q + j][4i .. 4i + 3]
@@ -2029,11 +1878,8 @@ __global__ void __launch_bounds__(256) wgrad_gw_kernel(const float* __restrict__
 // ------------------------------------------------------------------ dispatch ---
 // Environment knob MSHA_SKINNY=0 routes every call to the tiled GEMMs (A/B runs).
 static bool skinny_enabled() {
-  static const int on = [] {
-    const char* v = getenv("MSHA_SKINNY");
-    return v != nullptr && *v ? atoi(v) : 1;
-  }();
-  return on != 0;
+  static const bool on = env_int("MSHA_SKINNY", 1) != 0;
+  return on;
 }
 
 static int proj_grid(int64_t M, int waves = sk::kProjWaves) {
@@ -2062,10 +1908,7 @@ int skinny_project(int64_t M, int64_t K, int heads, int feat, const void* X, con
   // layer's input-gradient check on that graph then misses its bound in 1 of 6.4M
   // elements (1.07 x)
   constexpr bool kF32 = std::is_same<T, float>::value;
-  static const int64_t split_min = [] {
-    const char* v = getenv("MSHA_PROJ_SPLIT_MIN_ROWS");
-    return v != nullptr && *v ? (int64_t)atoll(v) : (int64_t)65536;
-  }();
+  static const int64_t split_min = env_int("MSHA_PROJ_SPLIT_MIN_ROWS", 65536);
   const bool split = kF32 && M >= split_min;
 #define SKP(k, n, fe)                                                                           \
   if (K == k && N == n && (score ? feat == fe : fe == 0)) {                                    \
@@ -2097,7 +1940,7 @@ template int skinny_project<bf16_t>(int64_t, int64_t, int, int, const void*, con
 
 // pair linear on the resident-W kernels: fp32, both gathers given, K and N in {64, 128},
 // 16-byte aligned rows; 0 = not covered (the caller runs the tiled GEMM).  Tables with
-// known row counts inside a 4 GiB buffer window take pair_roll_kernel.
+// known row counts inside a 4 GiB buffer window take pair_x3_kernel, the rest pair_kernel.
 int skinny_pair_linear(int64_t P, int64_t K, int64_t N, const float* G, int64_t ldg,
                        const int64_t* gi, const float* G2, int64_t ldg2, const int64_t* gj,
                        int64_t g_rows, int64_t g2_rows, const float* W, const float* bias,
@@ -2106,29 +1949,18 @@ int skinny_pair_linear(int64_t P, int64_t K, int64_t N, const float* G, int64_t 
   if (G2 == nullptr) { G2 = G; ldg2 = ldg; g2_rows = g_rows; }
   if (ldg % 4 || ldg2 % 4 || (((uintptr_t)G | (uintptr_t)G2 | (uintptr_t)out | (uintptr_t)W) & 15))
     return 0;
-  // MSHA_PAIR_ROLL: 2 (default) split-bf16 pair_x3_kernel, 1 the exact-fp32 rolling
-  // pair_roll_kernel, 0 always the two-register-set pair_kernel
-  static const int roll_env = [] {
-    const char* v = getenv("MSHA_PAIR_ROLL");
-    return v != nullptr && *v ? atoi(v) : 2;
-  }();
   // table bytes up to the last row's K columns (the kernel reads no further)
   auto span = [&](int64_t rows, int64_t ld) -> int64_t { return rows > 0 ? ((rows - 1) * ld + K) * 4 : -1; };
   const int64_t ba = span(g_rows, ldg), bb = span(g2_rows, ldg2);
-  const bool roll = roll_env && ba > 0 && bb > 0 && ba <= 0xFFFFFFFFll && bb <= 0xFFFFFFFFll &&
-                    P * N * 4 < (1ll << 31);
+  const bool window = ba > 0 && bb > 0 && ba <= 0xFFFFFFFFll && bb <= 0xFFFFFFFFll &&
+                      P * N * 4 < (1ll << 31);
   const dim3 grid(proj_grid(P)), block(64 * sk::kProjWaves);
-  constexpr int rw = 4 * PAIR32_WPS, xw = 4 * PAIR_X3_WPS;
-  const dim3 rgrid(proj_grid(P, rw)), rblock(64 * rw);
+  constexpr int xw = 4 * PAIR_X3_WPS;
   const dim3 xgrid(proj_grid(P, xw)), xblock(64 * xw);
 #define SKPL(k, n)                                                                              \
   if (K == k && N == n) {                                                                       \
-    if (roll && roll_env == 2)                                                                  \
+    if (window)                                                                                 \
       hipLaunchKernelGGL((sk::pair_x3_kernel<k, n, PAIR_X3_WPS>), xgrid, xblock, 0, s, (int)P,  \
-                         G, ldg, gi, G2, ldg2, gj, W, bias, act, dp, out, (uint32_t)ba,         \
-                         (uint32_t)bb);                                                         \
-    else if (roll)                                                                              \
-      hipLaunchKernelGGL((sk::pair_roll_kernel<k, n, PAIR32_WPS>), rgrid, rblock, 0, s, (int)P, \
                          G, ldg, gi, G2, ldg2, gj, W, bias, act, dp, out, (uint32_t)ba,         \
                          (uint32_t)bb);                                                         \
     else                                                                                        \
@@ -2192,19 +2024,15 @@ int skinny_dx(int64_t M, int64_t N, int64_t K, const float* Dh, const float* W, 
 // dW (128 x 128, fp32) = X^T D' over K rows: A = X^T given as (A, sAm = 1, sAk = ldx),
 // B = D' = D (+ head outer) given as (B, sBk = ldd, sBn = 1).  Uses the caller's split-K
 // workspace (splits x 128 x 128 fp32) for the block partials; 0 = not covered.
-int wgrad_x3(int64_t K, const float* X, int64_t ldx, const float* D, int64_t ldd, int hH, int hF,
-             const float* de, const float* a, const float* de2, const float* a2, float* slab,
-             int nb, const float* cs_tab, float* cs_part, hipStream_t s);
-
 // The fp32 weight gradient's kernel: MSHA_WGRAD=s3 (split-bf16, register operands, at any
-// size), x3 (split-bf16 through LDS images, wgrad_x3.hip) or fp32 (exact-fp32 MFMA,
-// wgrad_kernel); unset: s3 from MSHA_WGRAD_S3_MIN_ROWS (131,072) rows, fp32 below.
-// Switchable at run time (msha_wgrad_kernel) for A/B runs and tests.
+// size) or fp32 (exact-fp32 MFMA, wgrad_kernel); unset or any other word: s3 from
+// MSHA_WGRAD_S3_MIN_ROWS (131,072) rows, fp32 below.  Switchable at run time
+// (msha_wgrad_kernel: modes 0 auto, 1 fp32, 3 s3) for A/B runs and tests.
 static std::atomic<int>& wgrad_mode() {
   static std::atomic<int> m([] {
     const char* v = getenv("MSHA_WGRAD");
     if (v == nullptr || !*v) return 0;
-    return strcmp(v, "x3") == 0 ? 2 : strcmp(v, "fp32") == 0 ? 1 : strcmp(v, "s3") == 0 ? 3 : 0;
+    return strcmp(v, "fp32") == 0 ? 1 : strcmp(v, "s3") == 0 ? 3 : 0;
   }());
   return m;
 }
@@ -2234,10 +2062,7 @@ int skinny_wgrad(int64_t M, int64_t N, int64_t K, const float* A, int64_t sAm, i
   // gave the one-wave form's bits but no speed: with the h-table column sums 44.4-45.1 us
   // at 100k rows against 44.8-45.4 one wave and 43.3-45.5 exact fp32, 112-115 vs 97-103 us
   // at 262,144; X single-buffered and 12 registers of scratch at the 256-register limit.)
-  static const int64_t s3_min = [] {
-    const char* v = getenv("MSHA_WGRAD_S3_MIN_ROWS");
-    return v != nullptr && *v ? (int64_t)atoll(v) : (int64_t)131072;
-  }();
+  static const int64_t s3_min = env_int("MSHA_WGRAD_S3_MIN_ROWS", 131072);
   const int req = wgrad_mode().load();  // 3: the split kernel whatever the rows
   const int mode = req == 3 ? 0 : req == 0 && K < s3_min ? 1 : req;
   const bool small = K * sAk * 4 < (1ll << 31) && K * sBk * 4 < (1ll << 31);
@@ -2267,9 +2092,6 @@ int skinny_wgrad(int64_t M, int64_t N, int64_t K, const float* A, int64_t sAm, i
       hipLaunchKernelGGL((sk::wgrad_s3_kernel<false, 0>), dim3((unsigned)nb), dim3(64 * sk::kWsWaves),
                          0, s, (int)K, A, sAk, B, sBk, nullptr, nullptr, nullptr, nullptr, 1, 4, slab,
                          nullptr, nullptr);
-  } else if (mode == 2 &&
-             wgrad_x3(K, A, sAk, B, sBk, hH, hF, de, a, de2, a2, slab, (int)nb, cs_tab, cs_part, s)) {
-    // split-bf16 (wgrad_x3.hip): same slab / partial layout
   } else if (cs_tab != nullptr)
     hipLaunchKernelGGL((sk::wgrad_kernel<true, true>), dim3((unsigned)nb), dim3(64 * sk::kWgWaves), 0, s,
                        (int)K, A, sAk, B, sBk, de, a, de2, a2, hH, hF, slab, cs_tab, cs_part);
@@ -2294,10 +2116,10 @@ int skinny_wgrad(int64_t M, int64_t N, int64_t K, const float* A, int64_t sAm, i
 // kernels (slots x 64 uint64 words, device memory); MSHA_ERR_UNSUPPORTED unless the library
 // was built with -DSK_TIMELINE (build.py --variant timeline).
 // (ABI 15) the fp32 weight-gradient kernel: 0 auto (split-bf16 registers from 131,072 rows,
-// exact fp32 below), 1 exact fp32, 2 split-bf16 LDS images, 3 split-bf16 registers at any
-// size; returns the previous mode, mode < 0 only queries
+// exact fp32 below), 1 exact fp32, 3 split-bf16 registers at any size; returns the previous
+// mode, any other value only queries
 extern "C" int32_t msha_wgrad_kernel(int32_t mode) {
-  if (mode < 0 || mode > 3) return msha::wgrad_mode().load();
+  if (mode != 0 && mode != 1 && mode != 3) return msha::wgrad_mode().load();
   return msha::wgrad_mode().exchange(mode);
 }
 

@@ -505,6 +505,22 @@ def wgrad_kernel(request, msha):
     lib.msha_wgrad_kernel(prev)
 
 
+def test_wgrad_kernel_removed_mode_only_queries(msha):
+    """msha_wgrad_kernel(2), the number of a removed kernel, is out of range like any
+    other value outside 0, 1, 3: it returns the current mode and leaves it unchanged."""
+    from msha_gnn_amd import _lib
+
+    lib = _lib.load()
+    prev = lib.msha_wgrad_kernel(3)
+    try:
+        assert lib.msha_wgrad_kernel(2) == 3
+        assert lib.msha_wgrad_kernel(-1) == 3
+    finally:
+        lib.msha_wgrad_kernel(prev)
+    assert lib.msha_wgrad_kernel(2) == prev
+    assert lib.msha_wgrad_kernel(-1) == prev
+
+
 def _wgrad_bound(got, X, tot, name):
     """Every dW element within 4 sqrt(n) u sum_r |X[r, a]| |tot[r, n]| (n = rows + the
     split's six products and the block / slab reduce levels) of the fp64 product."""
@@ -854,9 +870,10 @@ def test_pair_linear_resident_w(cuda, msha, K, N):
     """msha_pair_linear on the resident-W kernels (skinny.hip, fp32, both gathers,
     P >= 1024): hadamard of the gathered rows @ W^T + b, ReLU, dropout keyed on p * N + n
     (the library's Philox mask), sigmoid -- vs the oracle with that mask; a ragged last
-    tile (P % 16 != 0).  Table row counts given -> pair_roll_kernel (one rolling row
-    set, buffer gathers, line-major k order); unknown (0) -> pair_kernel.  Both against
-    the oracle; they sum k in different orders, so they agree to rounding, not bits."""
+    tile (P % 16 != 0).  Table row counts given -> pair_x3_kernel (split-bf16 products,
+    one rolling row set, buffer gathers, line-major k order); unknown (0) -> pair_kernel
+    (exact-fp32 MFMA).  Both against the oracle; they sum k in different orders, so they
+    agree to rounding, not bits."""
     from msha_gnn_amd import _lib
     from msha_gnn_amd import functional as MF
 
