@@ -385,6 +385,29 @@ MSHA_API int msha_gemm_f32(int64_t M, int64_t N, int64_t K, const float* A, int6
                            int64_t ldc, float beta, int32_t splits, void* ws, size_t ws_bytes,
                            msha_stream_t stream);
 
+/* host-only (ABI 16, added): the operand staging the tiled kernels would use for these
+ * operands -- MSHA_GEMM_LOADER_SCALAR (element-wise, any strides) or MSHA_GEMM_LOADER_VEC
+ * (16-byte loads) or'ed with _AK (A's k is contiguous, else its m) and _BNF (B's n is
+ * contiguous, else its k).  The answer of the function the launch itself asks.
+ * msha_gemm_f32_loader: 16-byte staging needs, for each operand, unit stride along one
+ * dimension (B's n is tried before its k, A's k before its m), the other stride a multiple
+ * of 4, a 16-byte aligned base, and a multiple of 4 for the extent along the unit stride
+ * (K for a k-contiguous operand, M for an m-contiguous A, N for an n-contiguous B); one
+ * operand failing sends both to the scalar loader.  (The resident weight-gradient kernel
+ * takes M = N = 128, K >= 4096, splits >= 16 before the tiled kernel is asked.)
+ * msha_gemm_bf16_loader: -1 where msha_gemm_bf16 returns MSHA_ERR_UNSUPPORTED for an
+ * operand's layout (its rule is with msha_gemm_bf16 below; A's and B's k are tried first). */
+#define MSHA_GEMM_LOADER_SCALAR 0
+#define MSHA_GEMM_LOADER_BNF 1
+#define MSHA_GEMM_LOADER_AK 2
+#define MSHA_GEMM_LOADER_VEC 4
+MSHA_API int32_t msha_gemm_f32_loader(int64_t M, int64_t N, int64_t K, const float* A,
+                                      int64_t sAm, int64_t sAk, const float* B, int64_t sBk,
+                                      int64_t sBn);
+MSHA_API int32_t msha_gemm_bf16_loader(int64_t M, int64_t N, int64_t K, const void* A,
+                                       int64_t sAm, int64_t sAk, const void* B, int64_t sBk,
+                                       int64_t sBn);
+
 /* msha_gemm_f32 with the backward of msha_project_scores folded into one operand's
  * loads: operand 0 (A, M x K, K = heads*feat, sAk = 1) or 1 (B, K x N, N = heads*feat,
  * sBn = 1) is read as X + de (x) a [+ de2 (x) a2], i.e. X[r, c] + de[r, c/feat] a[c].

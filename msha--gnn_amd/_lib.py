@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("MSHA_GNN_LIB", os.path.join(_PKG, "lib", "libmsha_gnn
 
 ABI_VERSION = 16  # MSHA_ABI_VERSION of include/msha_gnn.h
 MSHA_OK, MSHA_ERR_ARG, MSHA_ERR_UNSUPPORTED, MSHA_ERR_HIP = 0, -1, -2, -3
+# MSHA_GEMM_LOADER_* (msha_gemm_f32_loader / msha_gemm_bf16_loader)
+GEMM_LOADER_SCALAR, GEMM_LOADER_BNF, GEMM_LOADER_AK, GEMM_LOADER_VEC = 0, 1, 2, 4
 
 
 class MshaLibraryError(RuntimeError):
@@ -206,6 +208,9 @@ SIGNATURES = {
     "msha_nll_rows_bwd_flags": (C.c_int, [I64, I64, I64, P, P, P, I32, P, I64, P, P, P]),
     "msha_head_bwd_flagged": (C.c_int, [GP, HPP, I32, P, P, P, F32, U64, F32, U64, P, P, P, P, P,
                                         P, P, P, I64, P, SZ, P]),
+    # operand-staging queries of the tiled GEMMs, host-only (ABI 16, added)
+    "msha_gemm_f32_loader": (I32, [I64, I64, I64, P, I64, I64, P, I64, I64]),
+    "msha_gemm_bf16_loader": (I32, [I64, I64, I64, P, I64, I64, P, I64, I64]),
     # device-side evaluation (ABI 16, added)
     "msha_eval_rows": (C.c_int, [I64, I32, I64, I32, P, I64, P, P, I64, P, P, P, P, P, P, P]),
     "msha_eval_loss": (C.c_int, [I64, I64, P, P, P]),

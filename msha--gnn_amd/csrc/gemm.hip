@@ -617,16 +617,28 @@ __global__ void __launch_bounds__(256) head_colsum_reduce_kernel(int nblk, int D
   if (lane == 0) out[d] = v;
 }
 
+// The one staging decision of the tiled kernel (msha_gemm_f32_loader reports it):
+// MSHA_GEMM_LOADER_SCALAR, or MSHA_GEMM_LOADER_VEC with the AK / BNF flags of the
+// 16-byte loaders (stage_load's template arguments).
+template <int AMODE>
+static int loader_of(const GemmArgs& p) {
+  if (!vec_ok<AMODE>(p)) return MSHA_GEMM_LOADER_SCALAR;
+  const bool ak = AMODE != A_STRIDED || p.sAk == 1;
+  const bool bn = p.sBn == 1;
+  return MSHA_GEMM_LOADER_VEC | (ak ? MSHA_GEMM_LOADER_AK : 0) | (bn ? MSHA_GEMM_LOADER_BNF : 0);
+}
+
 template <int AMODE, int EPI, int FEPI>
 static void launch(const GemmArgs& p, int splits, hipStream_t s) {
   dim3 grid((unsigned)((p.M + BM - 1) / BM), (unsigned)((p.N + BN - 1) / BN), (unsigned)splits);
-  if (!vec_ok<AMODE>(p)) {
+  const int ld = loader_of<AMODE>(p);
+  if (ld == MSHA_GEMM_LOADER_SCALAR) {
     hipLaunchKernelGGL((gemm_f32_kernel<AMODE, EPI, FEPI, LD_SCALAR, 1, 1>), grid, dim3(256), 0, s,
                        p);
     return;
   }
-  const bool ak = AMODE != A_STRIDED || p.sAk == 1;
-  const bool bn = p.sBn == 1;
+  const bool ak = (ld & MSHA_GEMM_LOADER_AK) != 0;
+  const bool bn = (ld & MSHA_GEMM_LOADER_BNF) != 0;
   if (AMODE != A_STRIDED || EPI != EPI_STORE) {  // projections / pair scorer: fixed layouts
     if (bn)
       hipLaunchKernelGGL((gemm_f32_kernel<AMODE, EPI, FEPI, LD_VEC, 1, 1>), grid, dim3(256), 0, s,
@@ -668,7 +680,9 @@ extern "C" size_t msha_gemm_workspace_size(int64_t M, int64_t N, int32_t splits)
 template <int HO>
 static void launch_ho(const GemmArgs& p, int splits, hipStream_t s) {
   dim3 grid((unsigned)((p.M + BM - 1) / BM), (unsigned)((p.N + BN - 1) / BN), (unsigned)splits);
-  const bool ak = p.sAk == 1, bn = p.sBn == 1;
+  // vector staging only (msha_gemm_f32_head_outer refuses the scalar loader)
+  const int ld = loader_of<A_STRIDED>(p);
+  const bool ak = (ld & MSHA_GEMM_LOADER_AK) != 0, bn = (ld & MSHA_GEMM_LOADER_BNF) != 0;
   if (HO == HO_A) {  // A has k contiguous
     if (bn)
       hipLaunchKernelGGL((gemm_f32_kernel<A_STRIDED, EPI_STORE, 0, LD_VEC, 1, 1, HO>), grid,
@@ -738,6 +752,16 @@ extern "C" int msha_gemm_f32(int64_t M, int64_t N, int64_t K, const float* A, in
   return gemm_run(p, HO_NONE, beta, splits, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// host-only (ABI 16, added): the staging msha_gemm_f32 would run on the tiled kernel
+extern "C" int32_t msha_gemm_f32_loader(int64_t M, int64_t N, int64_t K, const float* A,
+                                        int64_t sAm, int64_t sAk, const float* B, int64_t sBk,
+                                        int64_t sBn) {
+  GemmArgs p = base_args(M, N, K);
+  p.A = A; p.sAm = sAm; p.sAk = sAk;
+  p.B = B; p.sBk = sBk; p.sBn = sBn;
+  return loader_of<A_STRIDED>(p);
+}
+
 extern "C" int msha_gemm_f32_head_outer(int64_t M, int64_t N, int64_t K, const float* A,
                                         int64_t sAm, int64_t sAk, const float* B, int64_t sBk,
                                         int64_t sBn, float* C, int64_t ldc, float beta,
@@ -763,7 +787,7 @@ extern "C" int msha_gemm_f32_head_outer(int64_t M, int64_t N, int64_t K, const f
   p.de = de; p.ha = a; p.de2 = de2; p.ha2 = a2; p.hH = heads; p.hF = feat;
   const bool lay = operand == 0 ? sAk == 1 : sBn == 1;
   const bool al = aligned16(a) && (a2 == nullptr || aligned16(a2));
-  if (!lay || !al || !vec_ok<A_STRIDED>(p))
+  if (!lay || !al || loader_of<A_STRIDED>(p) == MSHA_GEMM_LOADER_SCALAR)
     return fail(MSHA_ERR_UNSUPPORTED, "gemm_f32_head_outer: the updated operand needs unit stride "
                                       "along heads*feat and 16-byte aligned, vectorizable operands");
   return gemm_run(p, operand == 0 ? HO_A : HO_B, beta, splits, ws, ws_bytes, (hipStream_t)stream);

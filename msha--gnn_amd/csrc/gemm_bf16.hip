@@ -410,6 +410,16 @@ static int layout_of(int64_t srow, int64_t sk, int64_t rows, int64_t K, const vo
   return 0;
 }
 
+// The one layout decision of msha_gemm_bf16 (msha_gemm_bf16_loader reports it): -1 when an
+// operand's layout is refused, else MSHA_GEMM_LOADER_VEC with AK (A k-contiguous) / BNF
+// (B n-contiguous)
+static int loader_of(int64_t M, int64_t N, int64_t K, const void* A, int64_t sAm, int64_t sAk,
+                     const void* B, int64_t sBk, int64_t sBn) {
+  bool ak = true, bk = true;
+  if (!layout_of(sAm, sAk, M, K, A, ak) || !layout_of(sBn, sBk, N, K, B, bk)) return -1;
+  return MSHA_GEMM_LOADER_VEC | (ak ? MSHA_GEMM_LOADER_AK : 0) | (bk ? 0 : MSHA_GEMM_LOADER_BNF);
+}
+
 }  // namespace bfg
 }  // namespace msha
 
@@ -419,6 +429,13 @@ using namespace msha::bfg;
 extern "C" size_t msha_gemm_bf16_workspace_size(int64_t M, int64_t N, int32_t splits) {
   if (splits <= 1) return 0;
   return (size_t)splits * (size_t)M * (size_t)N * sizeof(float);
+}
+
+// host-only (ABI 16, added): the operand loaders msha_gemm_bf16 would run, -1 = refused
+extern "C" int32_t msha_gemm_bf16_loader(int64_t M, int64_t N, int64_t K, const void* A,
+                                         int64_t sAm, int64_t sAk, const void* B, int64_t sBk,
+                                         int64_t sBn) {
+  return loader_of(M, N, K, A, sAm, sAk, B, sBk, sBn);
 }
 
 extern "C" int msha_gemm_bf16(int64_t M, int64_t N, int64_t K, const void* A, int64_t sAm,
@@ -439,8 +456,9 @@ extern "C" int msha_gemm_bf16(int64_t M, int64_t N, int64_t K, const void* A, in
   p.A = (const bf16_t*)A; p.sAm = sAm; p.sAk = sAk;
   p.B = (const bf16_t*)B; p.sBk = sBk; p.sBn = sBn;
   p.C = C; p.ldc = ldc; p.c_bf16 = c_dtype == MSHA_DTYPE_BF16;
-  bool ak = true, bk = true;
-  if (!layout_of(sAm, sAk, M, K, A, ak) || !layout_of(sBn, sBk, N, K, B, bk))
+  const int ld = loader_of(M, N, K, A, sAm, sAk, B, sBk, sBn);
+  const bool ak = (ld & MSHA_GEMM_LOADER_AK) != 0, bk = (ld & MSHA_GEMM_LOADER_BNF) == 0;
+  if (ld < 0)
     return fail(MSHA_ERR_UNSUPPORTED, "gemm_bf16: each operand needs one unit stride, the other "
                                       "a multiple of 8, its extent along the unit stride a "
                                       "multiple of 8, and a 16-byte aligned base");

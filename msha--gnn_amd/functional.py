@@ -576,9 +576,17 @@ class _MatMul(torch.autograd.Function):
 
 def _mm(A, B):
     if A.dtype == BF16 or B.dtype == BF16:
-        if B.shape[1] % 8 == 0:
+        A, B = A.to(BF16), B.to(BF16)
+        M, K = A.shape
+        N = B.shape[1]
+        # the bf16 kernel where it takes both operands as they lie (msha_gemm_bf16_loader:
+        # the launch's own layout decision) and C (N % 8 == 0); any other shape or view --
+        # a forward's N = 30 recipients, which is its backward's K -- runs fp32 operands
+        # on the exact-fp32 kernel, the result rounded to bf16
+        if N % 8 == 0 and _lib.fn("msha_gemm_bf16_loader")(
+                M, N, K, A.data_ptr(), A.stride(0), A.stride(1), B.data_ptr(), B.stride(0),
+                B.stride(1)) >= 0:
             return gemm(A, B)
-        # bf16 C needs N % 8 == 0: fp32 operands on the exact-fp32 kernel instead
         return gemm(A.float(), B.float()).to(BF16)
     return gemm(A.float(), B.float())
 

@@ -1,8 +1,21 @@
 """Shared helpers for the GPU parity tests (inputs, oracle adapters)."""
 import numpy as np
+import pytest
 import torch
 
 from oracle import gnn_oracle as O
+
+
+@pytest.fixture(params=["s3", "fp32"])
+def wgrad_kernel(request, msha):
+    """Run under each fp32 weight-gradient kernel: split-bf16 in registers (the default)
+    and the exact-fp32 MFMA (msha_wgrad_kernel)."""
+    from msha_gnn_amd import _lib
+
+    lib = _lib.load()
+    prev = lib.msha_wgrad_kernel({"s3": 3, "fp32": 1}[request.param])
+    yield request.param
+    lib.msha_wgrad_kernel(prev)
 
 
 def random_counts(rng, n, m, max_deg, empty_rows=(), hot_col=None, full_rows=()):

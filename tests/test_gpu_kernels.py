@@ -12,6 +12,7 @@ import torch
 
 from conftest import golden
 from gpu_helpers import bounded_close, edge_abs_terms, random_counts, t, tol_close, virtual_csr
+from gpu_helpers import wgrad_kernel  # noqa: F401  (fixture, shared with test_gpu_gemm_layouts.py)
 from oracle import gnn_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -491,18 +492,6 @@ def test_project_scores_fwd_bwd(cuda, M, K, H, F):
      + (rer * torch.tensor(dr, dtype=torch.float64)).sum()).backward()
     for got, want in zip(ts, rs):
         tol_close(got.grad.cpu().numpy(), want.grad.numpy(), 1e-4, 1e-5)
-
-
-@pytest.fixture(params=["s3", "fp32"])
-def wgrad_kernel(request, msha):
-    """Run under each fp32 weight-gradient kernel: split-bf16 in registers (the default)
-    and the exact-fp32 MFMA (msha_wgrad_kernel)."""
-    from msha_gnn_amd import _lib
-
-    lib = _lib.load()
-    prev = lib.msha_wgrad_kernel({"s3": 3, "fp32": 1}[request.param])
-    yield request.param
-    lib.msha_wgrad_kernel(prev)
 
 
 def test_wgrad_kernel_removed_mode_only_queries(msha):
