@@ -642,6 +642,36 @@ MSHA_API int msha_ours_intra_bwd(const msha_graph* g, const msha_groups* grp, in
                                  float* da4s, void* d_hs, void* ws, size_t ws_bytes,
                                  msha_stream_t stream);
 
+/* Split intra mode (Ablation.py:140-205, OursLayer2) (ABI 16, added: new symbols only, no
+ * existing signature or behaviour changes, so MSHA_ABI_VERSION stays 16).  City and
+ * province attention are normalised each by its own softmax; the score is constant along
+ * n, so the weights are 1 / |city(src_b)| and 1 / |prov(src_b)| and depend on no table:
+ *   u_out[n] = u_inter[n] + sum_{b: same city} drop h2[src_b] / |city(src_b)|
+ *                         + sum_{b: same province} drop h2[src_b] / |prov(src_b)|
+ * Arguments as msha_ours_intra_fwd without the score vectors and the inter statistics; the
+ * dropout draws are the same Philox keys.  bstat (B, heads, 8): the weights in slots 5 / 6,
+ * zeros elsewhere. */
+MSHA_API int msha_ours_split_fwd(const msha_graph* g, const msha_groups* grp, int64_t B,
+                                 const int64_t* src, int32_t heads, int32_t feat, int32_t dtype,
+                                 const void* h2, const void* u_inter, float drop_p,
+                                 uint64_t seed, uint64_t offset, float* bstat, void* u_out,
+                                 msha_stream_t stream);
+/* Its backward, two stages around the inter backward (which takes no row_coef here: the
+ * weights do not depend on the inter attention):
+ *   stage 0: G (B, 2, heads*feat) = group sums of dropout * dU; da3s, da4s (heads, feat)
+ *            are written as zeros (the score vectors cannot change the output).
+ *   stage 1: d_hs[src_b] += G3_b / |city| + G4_b / |prov| (per row, batch order; no float
+ *            atomics: bitwise repeatable).
+ * Stage 0 needs msha_ours_split_workspace_size(grp, B, heads, feat) bytes. */
+MSHA_API size_t msha_ours_split_workspace_size(const msha_groups* grp, int64_t B,
+                                               int32_t heads, int32_t feat);
+MSHA_API int msha_ours_split_bwd(const msha_graph* g, const msha_groups* grp, int64_t B,
+                                 const int64_t* src, int32_t heads, int32_t feat, int32_t dtype,
+                                 const float* bstat, const void* dU, int32_t stage,
+                                 float drop_p, uint64_t seed, uint64_t offset, float* G,
+                                 float* da3s, float* da4s, void* d_hs, void* ws,
+                                 size_t ws_bytes, msha_stream_t stream);
+
 
 /* ---- Model head (Ablation.py:273-277 + :298-301, Ours.py:100-109
  * + :163-167): for every row i of the source side

@@ -187,6 +187,12 @@ SIGNATURES = {
     "msha_ours_workspace_size": (SZ, [GRP, I64, I32, I32]),
     "msha_ours_intra_bwd": (C.c_int, [GP, GRP, I64, P, I32, I32, I32, P, P, P, P, P, I32, F32, F32,
                                       U64, U64, P, P, P, P, P, P, P, SZ, P]),
+    # split intra mode (OursLayer2) (ABI 16, added)
+    "msha_ours_split_fwd": (C.c_int, [GP, GRP, I64, P, I32, I32, I32, P, P, F32, U64, U64, P, P,
+                                      P]),
+    "msha_ours_split_workspace_size": (SZ, [GRP, I64, I32, I32]),
+    "msha_ours_split_bwd": (C.c_int, [GP, GRP, I64, P, I32, I32, I32, P, P, I32, F32, U64, U64, P,
+                                      P, P, P, P, SZ, P]),
     "msha_segments": (C.c_int, [I32, P, P]),
     "msha_adam_workspace_size": (SZ, []),
     "msha_adam_step": (C.c_int, [I32, P, C.c_double, C.c_double, C.c_double, C.c_double,

@@ -134,6 +134,32 @@ __global__ void __launch_bounds__(256) ours_prep_kernel(
   }
 }
 
+// Split intra mode (Ablation.py:140-205, OursLayer2): city and province attention are
+// normalised each by its own softmax, so the weights are w3 = 1 / c3, w4 = 1 / c4 of the
+// source's groups (the score is constant along n) and depend on no table: a thread per
+// (b, h) writes them, zeros in the other bstat slots.  Same ride-along reduce blocks.
+template <typename T>
+__global__ void __launch_bounds__(256) ours_split_prep_kernel(OursArgs a, float* __restrict__ bstat,
+                                                              BipReduce rd, int nprep) {
+  if ((int)blockIdx.x >= nprep) {
+    __shared__ float red[64][17];
+    bip_reduce_block<T, 256>(rd, (int)blockIdx.x - nprep, red);
+    return;
+  }
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.B * a.H;
+       t += (int64_t)nprep * blockDim.x) {
+    const int64_t i = a.src[t / a.H];
+    const int32_t g3 = a.gid3[i], g4 = a.gid4[i];
+    const float c3 = (float)(a.gptr3[g3 + 1] - a.gptr3[g3]);  // >= 1: i is a member
+    const float c4 = (float)(a.gptr4[g4 + 1] - a.gptr4[g4]);
+    float* o = bstat + t * BS_N;
+#pragma unroll
+    for (int k = 0; k < BS_N; ++k) o[k] = 0.f;
+    o[BS_W3] = 1.f / c3;
+    o[BS_W4] = 1.f / c4;
+  }
+}
+
 // ---------------------------------------------------------------- forward ---
 // u_out[n] = u_in[n] + sum_{b: city(src_b) = city(n)} drop * w3_b h2[src_b]
 //                    + sum_{b: prov(src_b) = prov(n)} drop * w4_b h2[src_b]
@@ -910,6 +936,51 @@ __global__ void __launch_bounds__(1024) ours_bwd_finish_kernel(
   }
 }
 
+// Split mode's finish: the weights hang on no table, so there is no scalar chain, no
+// row_coef and no bgrad: d_hs[src_b] += w3 G3 + w4 G4 (per row, batch order), a thread per
+// (b, d) of a source's first batch entry.  Blocks from nwork on run the deferred bipartite
+// reduce as in ours_bwd_finish_kernel.
+template <typename T>
+__global__ void __launch_bounds__(256) ours_split_finish_kernel(
+    OursArgs a, const float* __restrict__ bstat, const float* __restrict__ G,
+    T* __restrict__ d_hs, BipReduce rd, int nwork) {
+  if ((int)blockIdx.x >= nwork) {
+    __shared__ float red[64][17];
+    bip_reduce_block<T, 256>(rd, (int)blockIdx.x - nwork, red);
+    return;
+  }
+  __shared__ int64_t s_src[kFinishLds];
+  const int H = a.H, F = a.F, D = H * F;
+  const int64_t B = a.B;
+  const bool in_lds = B <= kFinishLds;
+  if (in_lds) {
+    for (int64_t t = threadIdx.x; t < B; t += blockDim.x) s_src[t] = a.src[t];
+    __syncthreads();
+  }
+  auto SRC = [&](int64_t b) { return in_lds ? s_src[b] : a.src[b]; };
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < B * D;
+       t += (int64_t)nwork * blockDim.x) {
+    const int64_t b = t / D;
+    const int d = (int)(t % D);
+    const int h = d / F;
+    const int64_t i = SRC(b);
+    bool first = true;
+    for (int64_t q = 0; q < b; ++q)
+      if (SRC(q) == i) {
+        first = false;
+        break;
+      }
+    if (!first) continue;
+    float s = 0.f;
+    for (int64_t q = b; q < B; ++q) {
+      if (SRC(q) != i) continue;
+      const float* st = bstat + (q * H + h) * BS_N;
+      s += st[BS_W3] * G[(q * 2 + 0) * D + d] + st[BS_W4] * G[(q * 2 + 1) * D + d];
+    }
+    d_hs[i * D + d] = from_f32<T>(to_f32(d_hs[i * D + d]) + s);
+  }
+}
+
 static int check(const msha_graph* g, const msha_groups* grp, int64_t B, const int64_t* src,
                  int32_t heads, int32_t feat) {
   MSHA_ARG_CHECK(g && g->rowptr && g->col && g->n_rows > 0 && g->n_cols > 0,
@@ -1121,4 +1192,144 @@ extern "C" int msha_ours_intra_bwd(const msha_graph* g, const msha_groups* grp, 
     launch_bwd<float>(a, stage, B, nck, heads, feat, bstat, dU, G, bgrad, row_coef, da3s, da4s,
                       d_hs, Gp, s);
   return check_launch("ours_intra_bwd");
+}
+
+// ---------------------------------------------------- split intra mode (OursLayer2) ---
+// Forward launches of the split mode: its own prep (a thread per (b, h), with the ride-along
+// reduce blocks), then the node pass of launch_fwd unchanged (same kernels, same grids; the
+// dispatch is restated here so that the joint mode's launcher stays as it is).
+template <typename T>
+static void launch_split_fwd(const OursArgs& a, const msha_graph* g, int64_t B,
+                             const void* u_inter, float* bstat, void* u_out, hipStream_t s) {
+  BipReduce rd{};
+  const bool fuse = bip_reduce_take(rd, s);
+  const int nprep = B > 0 ? (int)grid_for(B * a.H, 256) : 0;
+  if (fuse && rd.bf16 != (sizeof(T) == 2 ? 1 : 0)) {  // (not this launch's table type)
+    bip_reduce_run(rd, s);
+    rd = BipReduce{};
+  }
+  const int nred = fuse && rd.part != nullptr ? rd.blocks() : 0;
+  if (nprep + nred > 0)
+    hipLaunchKernelGGL(ours_split_prep_kernel<T>, dim3(nprep + nred), dim3(256), 0, s, a, bstat,
+                       rd, nprep);
+  const int D = a.H * a.F;
+  if (B > 0 && B <= 64 && D <= 256) {  // the batch staged in LDS (ours_fwd_lds_kernel)
+    const size_t lds = (size_t)B * (D + 2 * a.H) * sizeof(float) + 4 +
+                       kOursFwdWaves * 64 * (sizeof(uint16_t) + sizeof(uint2));
+    const dim3 grid(grid_for(g->n_rows, kOursFwdWaves, 4 * ours_cu_count()));
+    const bool pk = a.dp.active && msha_ours_pack_draws(-1) != 0;
+#define FWDL(kd)                                                                                 \
+  hipLaunchKernelGGL((pk ? ours_fwd_lds_kernel<T, kd, true> : ours_fwd_lds_kernel<T, kd, false>), grid, \
+                     dim3(64 * kOursFwdWaves), lds, s, a, (const float*)bstat, (const T*)u_inter,     \
+                     (T*)u_out)
+    if (D <= 64) FWDL(1);
+    else if (D <= 128) FWDL(2);
+    else FWDL(4);
+#undef FWDL
+    return;
+  }
+  const dim3 grid(grid_for(g->n_rows, 4, B <= 64 ? 2048 : 1 << 16));
+#define FWD(kd) hipLaunchKernelGGL((ours_fwd_kernel<T, kd>), grid, dim3(256), 0, s, a, \
+                                   (const float*)bstat, (const T*)u_inter, (T*)u_out)
+  if (D <= 64) FWD(1);
+  else if (D <= 128) FWD(2);
+  else if (D <= 256) FWD(4);
+  else FWD(8);
+#undef FWD
+}
+
+extern "C" int msha_ours_split_fwd(const msha_graph* g, const msha_groups* grp, int64_t B,
+                                   const int64_t* src, int32_t heads, int32_t feat, int32_t dtype,
+                                   const void* h2, const void* u_inter, float drop_p,
+                                   uint64_t seed, uint64_t offset, float* bstat, void* u_out,
+                                   msha_stream_t stream) {
+  if (int rc = check(g, grp, B, src, heads, feat)) return rc;
+  MSHA_ARG_CHECK(h2 && u_inter && bstat && u_out, "ours_split_fwd: null pointer");
+  MSHA_ARG_CHECK(dtype == MSHA_DTYPE_F32 || dtype == MSHA_DTYPE_BF16, "ours_split_fwd: bad dtype");
+  hipStream_t s = (hipStream_t)stream;
+  const OursArgs a = make_args(g, grp, B, src, heads, feat, h2, nullptr, nullptr, 0.f, drop_p,
+                               seed, offset, s);
+  if (dtype == MSHA_DTYPE_BF16)
+    launch_split_fwd<bf16_t>(a, g, B, u_inter, bstat, u_out, s);
+  else
+    launch_split_fwd<float>(a, g, B, u_inter, bstat, u_out, s);
+  return check_launch("ours_split_fwd");
+}
+
+extern "C" size_t msha_ours_split_workspace_size(const msha_groups* grp, int64_t B, int32_t heads,
+                                                 int32_t feat) {
+  return msha_ours_workspace_size(grp, B, heads, feat);
+}
+
+template <typename T>
+static void launch_split_bwd(const OursArgs& a, int stage, int64_t B, int nck, const float* bstat,
+                             const void* dU, float* G, float* zf, int64_t nz, void* d_hs,
+                             float* Gp, hipStream_t s) {
+  const int D = a.H * a.F;
+  if (stage == 0) {
+    const dim3 grid(grid_for(2 * B * nck, 4));
+#define GATHER(kd) hipLaunchKernelGGL((ours_bwd_gather_kernel<T, kd>), grid, dim3(256), 0, s, a, \
+                                      (const T*)dU, nck, Gp)
+    if (D <= 64) GATHER(1);
+    else if (D <= 128) GATHER(2);
+    else if (D <= 256) GATHER(4);
+    else GATHER(8);
+#undef GATHER
+    // (its zero fill writes da3s / da4s here: there is no row_coef in this mode)
+    hipLaunchKernelGGL(ours_bwd_gather_reduce_kernel, dim3(grid_for(2 * B * D, 256, 4096)),
+                       dim3(256), 0, s, B, D, nck, (const float*)Gp, G, zf, nz);
+    return;
+  }
+  // + the bipartite backward's d_hc / d_er reduce, when it was handed over
+  BipReduce rd{};
+  const bool fuse = bip_reduce_take(rd, s);
+  const int nwork = (int)grid_for(B * D, 256, 1024);
+  if (fuse && rd.bf16 != (sizeof(T) == 2 ? 1 : 0)) {  // (not this launch's table type)
+    bip_reduce_run(rd, s);
+    rd = BipReduce{};
+  }
+  const int nred = fuse && rd.part != nullptr ? rd.blocks() : 0;
+  hipLaunchKernelGGL(ours_split_finish_kernel<T>, dim3(nwork + nred), dim3(256), 0, s, a, bstat,
+                     (const float*)G, (T*)d_hs, rd, nwork);
+}
+
+extern "C" int msha_ours_split_bwd(const msha_graph* g, const msha_groups* grp, int64_t B,
+                                   const int64_t* src, int32_t heads, int32_t feat, int32_t dtype,
+                                   const float* bstat, const void* dU, int32_t stage,
+                                   float drop_p, uint64_t seed, uint64_t offset, float* G,
+                                   float* da3s, float* da4s, void* d_hs, void* ws,
+                                   size_t ws_bytes, msha_stream_t stream) {
+  if (int rc = check(g, grp, B, src, heads, feat)) return rc;
+  MSHA_ARG_CHECK(stage == 0 || stage == 1, "ours_split_bwd: stage must be 0 or 1");
+  MSHA_ARG_CHECK(dtype == MSHA_DTYPE_F32 || dtype == MSHA_DTYPE_BF16, "ours_split_bwd: bad dtype");
+  MSHA_ARG_CHECK(bstat && G, "ours_split_bwd: null pointer");
+  MSHA_ARG_CHECK(stage == 1 || (dU && da3s && da4s), "ours_split_bwd: stage 0 outputs");
+  MSHA_ARG_CHECK(stage == 0 || d_hs, "ours_split_bwd: stage 1 needs d_hs");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t D = (int64_t)heads * feat;
+  const bool joined = stage == 0 && da4s == da3s + D;  // one zero fill inside the reduce launch
+  if (stage == 0 && (B == 0 || !joined)) {
+    if (hipMemsetAsync(da3s, 0, sizeof(float) * D, s) != hipSuccess ||
+        hipMemsetAsync(da4s, 0, sizeof(float) * D, s) != hipSuccess)
+      return check_launch("ours_split_bwd memset");
+  }
+  if (B == 0) return MSHA_OK;
+  const OursArgs a = make_args(g, grp, B, src, heads, feat, nullptr, nullptr, nullptr, 0.f,
+                               drop_p, seed, offset, s);
+  int nck = 0;
+  float* Gp = nullptr;
+  if (stage == 0) {
+    const int maxg = grp->max_group > 0 ? grp->max_group : (int)g->n_rows;
+    nck = (maxg + kGatherChunk - 1) / kGatherChunk;
+    MSHA_ARG_CHECK(ws && ws_bytes >= msha_ours_workspace_size(grp, B, heads, feat),
+                   "ours_split_bwd: workspace too small");
+    Gp = (float*)ws;
+  }
+  float* zf = joined ? da3s : nullptr;
+  const int64_t nz = joined ? 2 * D : 0;
+  if (dtype == MSHA_DTYPE_BF16)
+    launch_split_bwd<bf16_t>(a, stage, B, nck, bstat, dU, G, zf, nz, d_hs, Gp, s);
+  else
+    launch_split_bwd<float>(a, stage, B, nck, bstat, dU, G, zf, nz, d_hs, Gp, s);
+  return check_launch("ours_split_bwd");
 }

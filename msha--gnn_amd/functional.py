@@ -2085,6 +2085,125 @@ class _OursAttention(torch.autograd.Function):
         return d_el, d_er, d_hc, d_hs, da3s, da4s, None, None, None, None, None, None
 
 
+class _OursSplitAttention(torch.autograd.Function):
+    """Ablation.py:165-202 core (OursLayer2): the inter attention (u, v) exactly as
+    edge_attention computes it, plus the batch intra attention with city and province each
+    under its own softmax, added to u (msha_ours_split_fwd / _bwd).  The intra weights are
+    1 / group size, so the backward has no term into el / er / lse and a3s / a4s get exact
+    zeros (their reference gradient is rounding noise around 0)."""
+
+    @staticmethod
+    def forward(ctx, el, er, h1, h2, a3s, a4s, graph: Graph, groups, src, p: float, seed: int,
+                slope: float):
+        n, H = el.shape
+        m, _, Fd = h1.shape
+        dt = _table_dtype(h1, h2)
+        el, er, h1, h2 = _f32c(el), _f32c(er), _tc(h1, dt), _tc(h2, dt)
+        src = src.to(torch.int64).contiguous()
+        B = src.numel()
+        dev = el.device
+        s = _stream(el)
+        g = graph.desc
+        u_inter = torch.empty(n, H, Fd, device=dev, dtype=dt)
+        bip = bip_ok(graph, H, Fd, dt)
+        u_lo = (torch.empty_like(u_inter) if dt == BF16 and not bip
+                and any(ctx.needs_input_grad[:4]) else None)
+        lse = torch.empty(n, H, device=dev, dtype=torch.float32)
+        v = torch.empty(m, H, Fd, device=dev, dtype=dt)
+        bstat = torch.empty(max(B, 1), H, 8, device=dev, dtype=torch.float32)
+        u = torch.empty_like(u_inter)
+        defer = bip and BIP_DEFER_REDUCE
+        try:
+            if bip:
+                ws = _bip_ws(graph, H, Fd, dev)
+                if defer:
+                    _lib.call("msha_bip_defer_reduce", 1)
+                _lib.call("msha_bip_attention_fwd", g, H, Fd, _code(dt), el.data_ptr(),
+                          er.data_ptr(), h1.data_ptr(), h2.data_ptr(), slope, p, seed, 0,
+                          u_inter.data_ptr(), None, lse.data_ptr(), None, v.data_ptr(),
+                          ws.data_ptr(), ws.numel(), s)
+            else:
+                attd = torch.empty(max(graph.n_edges, 1), H, device=dev, dtype=torch.float32)
+                _lib.call("msha_edge_attention_fwd", g, H, Fd, _code(dt), el.data_ptr(),
+                          er.data_ptr(), h1.data_ptr(), slope, p, seed, 0, u_inter.data_ptr(),
+                          _lib.ptr(u_lo), lse.data_ptr(), attd.data_ptr(), s)
+                _csc_aggregate(graph, H, Fd, attd, None, h2, v, None, s)
+            _lib.call("msha_ours_split_fwd", g, groups.desc, B, src.data_ptr(), H, Fd,
+                      _code(dt), h2.data_ptr(), u_inter.data_ptr(), p, seed, 0,
+                      bstat.data_ptr(), u.data_ptr(), s)
+        finally:
+            if defer:
+                _lib.call("msha_bip_defer_reduce", 0)  # (launches it if still pending)
+        ctx.bip = bip
+        ctx.graph, ctx.groups, ctx.p, ctx.seed, ctx.slope = graph, groups, p, seed, slope
+        ctx.a_meta = (a3s.shape, a3s.dtype, a4s.shape, a4s.dtype)
+        # the bipartite backward recomputes from (el, er, lse); the row form also reads the
+        # inter aggregate.  The score vectors are not saved: nothing depends on them.
+        empty = el.new_empty(0)
+        ctx.save_for_backward(el, er, h1, h2, lse, bstat, src, empty if bip else u_inter,
+                              u_lo if u_lo is not None else empty)
+        ctx.mark_non_differentiable(bstat)
+        ctx.set_materialize_grads(False)
+        return u, v, bstat
+
+    @staticmethod
+    def backward(ctx, dU, dV, _bstat=None):
+        el, er, h1, h2, lse, bstat, src, u_inter, u_lo = ctx.saved_tensors
+        u_lo = u_lo if u_lo.numel() else None
+        graph, groups = ctx.graph, ctx.groups
+        n, H = el.shape
+        m, _, Fd = h1.shape
+        B = src.numel()
+        dev = el.device
+        s = _stream(el)
+        g, gr = graph.desc, groups.desc
+        dt = h1.dtype
+        dU = torch.zeros(n, H, Fd, device=dev, dtype=dt) if dU is None else _tc(dU, dt)
+        dV = torch.zeros(m, H, Fd, device=dev, dtype=dt) if dV is None else _tc(dV, dt)
+        G = torch.empty(max(B, 1), 2, H * Fd, device=dev, dtype=torch.float32)
+        das = torch.empty(2, H, Fd, device=dev, dtype=torch.float32)  # zeroed by stage 0
+        args = (g, gr, B, src.data_ptr(), H, Fd, _code(dt), bstat.data_ptr())
+        ws = _workspace(dev, _memo(groups, ("ours_ws", B, H, Fd), lambda: int(
+            _lib.fn("msha_ours_split_workspace_size")(gr, B, H, Fd))))
+        _lib.call("msha_ours_split_bwd", *args, dU.data_ptr(), 0, ctx.p, ctx.seed, 0,
+                  G.data_ptr(), das[0].data_ptr(), das[1].data_ptr(), None, ws.data_ptr(),
+                  ws.numel(), s)
+        d_el = torch.empty(n, H, device=dev, dtype=torch.float32)
+        d_hs = torch.empty(n, H, Fd, device=dev, dtype=dt)
+        d_hc = torch.empty(m, H, Fd, device=dev, dtype=dt)
+        d_er = torch.empty(m, H, device=dev, dtype=torch.float32)
+        sh3, dt3, sh4, dt4 = ctx.a_meta
+        da3s, da4s = das[0].view(sh3).to(dt3), das[1].view(sh4).to(dt4)
+        if ctx.bip:
+            ws = _bip_ws(graph, H, Fd, dev)
+            defer = BIP_DEFER_REDUCE
+            try:
+                if defer:
+                    _lib.call("msha_bip_defer_reduce", 1)
+                _lib.call("msha_bip_attention_bwd", g, H, Fd, _code(dt), el.data_ptr(),
+                          er.data_ptr(), h1.data_ptr(), lse.data_ptr(), dU.data_ptr(),
+                          h2.data_ptr(), dV.data_ptr(), None, ctx.slope, ctx.p, ctx.seed, 0,
+                          d_el.data_ptr(), d_er.data_ptr(), d_hc.data_ptr(), d_hs.data_ptr(),
+                          ws.data_ptr(), ws.numel(), s)
+                _lib.call("msha_ours_split_bwd", *args, None, 1, ctx.p, ctx.seed, 0,
+                          G.data_ptr(), None, None, d_hs.data_ptr(), None, 0, s)
+            finally:
+                if defer:
+                    _lib.call("msha_bip_defer_reduce", 0)
+            return d_el, d_er, d_hc, d_hs, da3s, da4s, None, None, None, None, None, None
+        E = max(graph.n_edges, 1)
+        rec = torch.empty(E, 2, H, device=dev, dtype=torch.float32)  # (de, attd) per edge
+        de, attd = rec[:, 0], rec[:, 1]
+        _lib.call("msha_edge_attention_bwd_rows", g, H, Fd, _code(dt), el.data_ptr(), er.data_ptr(),
+                  h1.data_ptr(), lse.data_ptr(), u_inter.data_ptr(), _lib.ptr(u_lo), dU.data_ptr(),
+                  h2.data_ptr(), dV.data_ptr(), None, ctx.slope, ctx.p, ctx.seed, 0,
+                  d_el.data_ptr(), de.data_ptr(), attd.data_ptr(), 2 * H, d_hs.data_ptr(), s)
+        _lib.call("msha_ours_split_bwd", *args, None, 1, ctx.p, ctx.seed, 0, G.data_ptr(), None,
+                  None, d_hs.data_ptr(), None, 0, s)
+        _csc_aggregate(graph, H, Fd, attd, de, dU, d_hc, d_er, s, ld=2 * H)
+        return d_el, d_er, d_hc, d_hs, da3s, da4s, None, None, None, None, None, None
+
+
 def ours_attention(graph: Graph, groups, src, el, er, h1, h2, a3s, a4s, p: float = 0.0,
                    training: bool = False, slope: float = NEG_SLOPE, seed: int | None = None,
                    return_aux: bool = False):
@@ -2102,6 +2221,28 @@ def ours_attention(graph: Graph, groups, src, el, er, h1, h2, a3s, a4s, p: float
     u, v, attd, bstat = _OursAttention.apply(el, er, h1, h2, a3s, a4s, graph, groups, src, p,
                                              seed, slope)
     return (u, v, attd, bstat) if return_aux else (u, v)
+
+
+def ours_split_attention(graph: Graph, groups, src, el, er, h1, h2, a3s, a4s, p: float = 0.0,
+                         training: bool = False, slope: float = NEG_SLOPE,
+                         seed: int | None = None, return_aux: bool = False):
+    """OursLayer2's attention core (Ablation.py:165-202): ``ours_attention`` with city and
+    province attention each under its own softmax instead of the joint normaliser.  Returns
+    (u, v); with return_aux also bstat (B, H, 8) (the intra weights 1 / group size in slots
+    5 / 6).  a3s / a4s cannot change the output and get exact zero gradients; the dropout
+    draws are ``ours_attention``'s (same Philox keys)."""
+    _lib.require_cuda(el, er, h1, h2, a3s, a4s, src)
+    H, Fd = el.shape[1], h1.shape[-1]
+    if not _lib.load().msha_edge_attention_supported(H, Fd):
+        raise NotImplementedError(f"ours_split_attention: (heads={H}, feat={Fd}) not compiled")
+    if H * Fd > 512:
+        raise NotImplementedError("ours_split_attention: heads*feat must be <= 512")
+    p = float(p) if training else 0.0
+    if seed is None:
+        seed = new_seed() if p > 0 else 0
+    u, v, bstat = _OursSplitAttention.apply(el, er, h1, h2, a3s, a4s, graph, groups, src, p,
+                                            seed, slope)
+    return (u, v, bstat) if return_aux else (u, v)
 
 
 # ------------------------------------------------------------------ model head ---

@@ -9,6 +9,8 @@ and RNG consumption order as the reference, so a model built after
   LLPGAT                LLP.py:148-168     (GAT whose forward takes external features)
   OursLayer3            Ablation.py:235-277
   ablation3             Ablation.py:279-301  (its heads run as ONE multi-head launch)
+  OursLayer2, ablation2 Ablation.py:140-231  (city / province attention each under its
+                                              own softmax; heads as one launch set)
   LinkPredictor         LLP.py:86-115
   MLP                   LLP.py:36-84       (the student encoder; norm_type 'none' only)
   OursLayer, Ours       Ours.py:29-167 (full MSHA: inter + city/province attention)
@@ -583,6 +585,87 @@ class Ours(nn.Module):
         u, v = _attention_uv(self.attentions, s_input, r_input, g, city_adj, province_adj,
                              source_index, self.training, record, Coeff12, Coeff3, Coeff4,
                              packed)
+        if _head_fusable(self.attentions, g, self.training):
+            return _model_tail(self, g, u, v)
+        return _tail_unfused(self, g, u, v)
+
+
+def _attention_uv2(heads, s_input, r_input, graph: Graph, city_adj, province_adj, source_index,
+                   training, packed=False):
+    """OursLayer2 inter + split intra attention of all heads: (u (N, H, F), v (M, H, F)).
+    ``_attention_aux``'s projections and packing, then ``functional.ours_split_attention``."""
+    H = len(heads)
+    Fd = heads[0].out_features
+    n, m = s_input.shape[0], r_input.shape[0]
+    if graph.n_cols != m or graph.n_rows != n:
+        raise ValueError(f"inter_adj is {graph.n_rows}x{graph.n_cols}, features are {n} "
+                         f"sources x {m} recipients")
+    groups = groups_for(city_adj, province_adj, s_input.device)
+    if packed is False:
+        packed = MF.pack_heads(heads, intra=True)
+    if packed is not None:  # one launch (and one in the backward)
+        W1, W2, a_r, a_l, a3s, a4s = packed
+    else:
+        W1 = heads[0].W1 if H == 1 else torch.cat([h.W1 for h in heads], dim=1)
+        W2 = heads[0].W2 if H == 1 else torch.cat([h.W2 for h in heads], dim=1)
+        a_r, a_l = _score_halves(heads, "a").unbind(1)
+        a3s = _score_halves(heads, "a3").sum(1)
+        a4s = _score_halves(heads, "a4").sum(1)
+    h1, er = MF.project_scores(r_input, W1, ar=a_r, heads=H)
+    h2, el = MF.project_scores(s_input, W2, al=a_l, heads=H)
+    src = torch.as_tensor(source_index, device=s_input.device)
+    return MF.ours_split_attention(graph, groups, src, el, er, h1.view(m, H, Fd),
+                                   h2.view(n, H, Fd), a3s, a4s, p=heads[0].dropout,
+                                   training=training)
+
+
+class OursLayer2(OursLayer3):
+    """Ablation.py:140-205: OursLayer whose city and province attention are normalised
+    each by its own softmax instead of the joint SUM_county.  The score of a batch entry
+    is constant along its row, so the attention is 1 / group size on the source's group:
+    a3 / a4 cannot change the output and receive exact zero gradients (the reference's are
+    rounding noise around 0)."""
+
+    def forward(self, Sinput, Rinput, inter_adj, city_adj, province_adj, source_index):
+        u, v = _attention_uv2([self], Sinput, Rinput, _graph(inter_adj), city_adj, province_adj,
+                              source_index, self.training)
+        return _epilogues([self], u.unbind(1), v.unbind(1))[0]
+
+
+class ablation2(nn.Module):  # noqa: N801  (reference class name)
+    """Ablation.py:208-231: n_heads OursLayer2 (one fused launch set) -> cat -> dropout ->
+    GAL -> elu -> log_softmax.  The record arguments are accepted and ignored, as in the
+    reference (Ablation.py:224-231)."""
+
+    def __init__(self, in_features, out_features, n_classes, n_heads, dropout, gdp, Scount,
+                 Rcount):
+        super().__init__()
+        self.Sfeatures = _features_with_gdp(Scount, in_features, gdp)
+        self.Rfeatures = nn.Parameter(torch.rand([Rcount, in_features]))
+        self.n_classes = n_classes
+        self.n_heads = n_heads
+        self.dropout = dropout
+        self.attentions = [OursLayer2(in_features, out_features, dropout=dropout)
+                           for _ in range(n_heads)]
+        for i, attention in enumerate(self.attentions):
+            self.add_module(f"attention_{i}", attention)
+        self.out_att = GraphAttentionLayer(n_classes * n_heads, n_classes, dropout=dropout)
+
+    def forward(self, inter_adj, city_adj, province_adj, source_index, record=False,
+                Coeff12=None, Coeff3=None, Coeff4=None):
+        if replay.eligible(self, source_index):  # replay.py
+            return replay.run(self, lambda s: self._forward(inter_adj, city_adj, province_adj,
+                                                             s),
+                              (inter_adj, city_adj, province_adj), source_index)
+        return self._forward(inter_adj, city_adj, province_adj, source_index)
+
+    def _forward(self, inter_adj, city_adj, province_adj, source_index):
+        g = _graph(inter_adj)
+        s_input, r_input, packed = MF.model_prologue(self.Sfeatures, self.Rfeatures,
+                                                     self.dropout, self.training,
+                                                     self.attentions, intra=True)
+        u, v = _attention_uv2(self.attentions, s_input, r_input, g, city_adj, province_adj,
+                              source_index, self.training, packed)
         if _head_fusable(self.attentions, g, self.training):
             return _model_tail(self, g, u, v)
         return _tail_unfused(self, g, u, v)

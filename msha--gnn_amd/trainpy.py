@@ -80,8 +80,9 @@ def namespace(data_dir, device, year="2015"):
 
 class TrainPy:
     """train.py:180-213 on a namespace from ``namespace``; ``model_kind`` 'ablation3'
-    (the model train.py:206 builds) or 'Ours' (the full MSHA model train.py:44-176
-    defines)."""
+    (the model train.py:206 builds), 'ablation2' (``from Ablation import *``'s model with
+    the split intra attention, built with the same arguments) or 'Ours' (the full MSHA
+    model train.py:44-176 defines)."""
 
     def __init__(self, ns, device, dropout=0.5, model_kind="ablation3", seed=0,
                  batch_size=64, dtype=None):
@@ -102,9 +103,9 @@ class TrainPy:
         province_adj = nrm(province_adj)
         GDP = Dataset.get_gdp()
         torch.manual_seed(seed)
-        if model_kind == "ablation3":
-            model = ns["ablation3"](in_features=128, out_features=64, n_classes=Rcount, n_heads=2,
-                                    dropout=dropout, gdp=GDP, Scount=Scount, Rcount=Rcount)
+        if model_kind in ("ablation2", "ablation3"):
+            model = ns[model_kind](in_features=128, out_features=64, n_classes=Rcount, n_heads=2,
+                                   dropout=dropout, gdp=GDP, Scount=Scount, Rcount=Rcount)
         else:  # train.py's Ours(in, out, classes, heads, dropout, gdp, Scount, Rcount)
             import Ours as _ours  # noqa: N813  (the drop-in module, first on sys.path)
 
