@@ -1240,6 +1240,59 @@ MSHA_API int msha_link_match_bwd(int32_t feat, int32_t h_dtype, const void* h, i
                                  int64_t n_t, const float* coef, const float* gloss, float* dH,
                                  msha_stream_t stream); /* (ABI 16, added) */
 
+/* ---- Link-prediction training of the 'mlp' predictor with one used Linear (LLP.py:233,
+ * :235, :238) (ABI 16, added) ------------------------------------------------------------
+ *   x_p   = h[src_p] * h[dst_p],  out_p = sigmoid(dropout(relu(W x_p + bias)))   (n_pairs, hidden)
+ *   L_lab = -(1 / Pv) sum_p out_p[label_p]                     F.nll_loss(out, label), mean
+ *   L_mse = (1 / (Pv hidden)) sum_p sum_j (out_pj - t_pj)^2    F.mse_loss(out, teacher_out), mean
+ *   terms = {w_label L_lab + w_mse L_mse, L_lab, L_mse}
+ * h (n, feat) fp32 or bf16 (row pitch ld elements, 16-byte aligned rows); W (hidden, feat) in
+ * h's dtype, contiguous; bias fp32; label int64 (n_pairs), NULL: dst itself; teacher_out
+ * (n_pairs, hidden) fp32, nullable (L_mse = 0).  feat and hidden powers of two in [16, 128]
+ * (msha_link_mlp_supported; feat also under msha_link_bce_supported).  A pair whose src or
+ * dst lies outside [0, n) or whose label lies outside [0, hidden) is padding: it enters no
+ * sum and not Pv, its out row is NaN, and no index reads outside h.  out is written by the
+ * gathered msha_pair_linear / msha_pair_linear_bf16 launch (act = bias | relu | [dropout] |
+ * sigmoid, the same Philox keys p * hidden + j) on pair lists whose padding entries read
+ * row 0; one pass then forms Pv (n_valid[0], counted on the device) and the two sums by
+ * per-block partials added in a fixed order (no float atomics).  Pv = 0 gives zeros.
+ * loss (nullable) receives terms[0] as a scalar of its own.
+ * ws: msha_link_mlp_loss_fwd_workspace_size bytes, 16-byte aligned.  Nothing is read back. */
+MSHA_API int msha_link_mlp_supported(int32_t feat, int32_t hidden, int32_t dtype); /* host-only (ABI 16, added) */
+MSHA_API int32_t msha_link_mlp_wgrad_rows(void); /* host-only (ABI 16, added) */
+MSHA_API size_t msha_link_mlp_loss_fwd_workspace_size(int64_t n_pairs); /* (ABI 16, added) */
+MSHA_API int msha_link_mlp_loss_fwd(int64_t n_pairs, int32_t feat, int32_t hidden, int32_t dtype,
+                                    const void* h, int64_t ld, int64_t n, const int64_t* src,
+                                    const int64_t* dst, const int64_t* label, const void* W,
+                                    const float* bias, const float* teacher_out, float w_label,
+                                    float w_mse, float drop_p, uint64_t seed, uint64_t offset,
+                                    float* out, float* terms, float* loss, int32_t* n_valid,
+                                    void* ws, size_t ws_bytes, msha_stream_t stream); /* (ABI 16, added) */
+/* Its backward from the stored out and n_valid, gloss a DEVICE scalar (ABI 16, added):
+ *   g_pj = gloss (-w_label / Pv [j == label_p] + 2 w_mse (out_pj - t_pj) / (Pv hidden))
+ *   dz   = g out (1 - out) / (1 - drop_p) where out > 0.5, else 0 (msha_pair_mlp_dz's rule);
+ *          (n_pairs, hidden) fp32, rows of padding pairs zero
+ *   dW   = dz^T (h[src] * h[dst]) (hidden, feat) and db = colsum(dz), fp32: the A operand is
+ *          gathered and multiplied in the loader of a v_mfma_f32_16x16x4_f32 kernel; pairs
+ *          are cut into blocks of msha_link_mlp_wgrad_rows(), one partial per block, added in
+ *          block order.  dW and db both NULL: skipped.
+ *   dx   = dz W32 (n_pairs, feat) fp32 on msha_gemm_f32 (W32: the forward's W as fp32)
+ *   dH[r] = sum over r's endpoints e in plan order of dx[p(e)] * h[other(e)], (n, feat) fp32,
+ *          every row written (zeros without endpoints), by the chunked row pass of
+ *          msha_link_bce_bwd with a row factor.  dH NULL: dx and the plan are not used.
+ * Bitwise reproducible: a function of the inputs and the plan alone.
+ * ws: msha_link_mlp_bwd_workspace_size bytes, 16-byte aligned. */
+MSHA_API size_t msha_link_mlp_bwd_workspace_size(int64_t n_pairs, int32_t feat, int32_t hidden); /* (ABI 16, added) */
+MSHA_API int msha_link_mlp_bwd(int64_t n_pairs, int32_t feat, int32_t hidden, int32_t dtype,
+                               const void* h, int64_t ld, int64_t n, const int64_t* src,
+                               const int64_t* dst, const int64_t* label, const float* W32,
+                               const float* teacher_out, const float* out,
+                               const int32_t* n_valid, float w_label, float w_mse, float drop_p,
+                               const float* gloss, const int32_t* plan_rowptr,
+                               const int32_t* plan_ent, const int32_t* plan_chunk_tab, float* dz,
+                               float* dx, float* dW, float* db, float* dH, void* ws,
+                               size_t ws_bytes, msha_stream_t stream); /* (ABI 16, added) */
+
 #ifdef __cplusplus
 }
 #endif

@@ -274,6 +274,15 @@ SIGNATURES = {
     "msha_link_match_fwd": (C.c_int, [I64, I32, I32, P, I64, I64, I32, P, I64, I64, P, P, P, P, P,
                                       P, P, SZ, P]),
     "msha_link_match_bwd": (C.c_int, [I32, I32, P, I64, I64, I32, P, I64, I64, P, P, P, P]),
+    # 'mlp' predictor training loss (ABI 16, added)
+    "msha_link_mlp_supported": (C.c_int, [I32, I32, I32]),
+    "msha_link_mlp_wgrad_rows": (I32, []),
+    "msha_link_mlp_loss_fwd_workspace_size": (SZ, [I64]),
+    "msha_link_mlp_loss_fwd": (C.c_int, [I64, I32, I32, I32, P, I64, I64, P, P, P, P, P, P, F32,
+                                         F32, F32, U64, U64, P, P, P, P, P, SZ, P]),
+    "msha_link_mlp_bwd_workspace_size": (SZ, [I64, I32, I32]),
+    "msha_link_mlp_bwd": (C.c_int, [I64, I32, I32, I32, P, I64, I64, P, P, P, P, P, P, P, F32, F32,
+                                    F32, P, P, P, P, P, P, P, P, P, P, SZ, P]),
 }
 
 _lib = None

@@ -177,6 +177,128 @@ static inline int pg_table_check(const char* name, int64_t n_pairs, int32_t feat
   return MSHA_OK;
 }
 
+// ---- vector factor (link_mlp_bwd, linkmlp.hip): the factor of endpoint e is the fp32 row
+// dx[p(e)], not a scalar:
+//
+//   dH[r] = sum over row r's endpoints e, in plan order, of dx[p(e)] * h[other(e)]
+//
+// The plan, the chunk partials, the chunk-order finish and the lane-group xor tree are the
+// scalar variant's, so the result is again a function of the plan alone.
+template <typename T>
+struct PgVecArgs {
+  int64_t P, n, ld;
+  int F;
+  const T* h;
+  const int64_t *src, *dst;
+  const float* dx;  // (P, F) fp32, pitch F
+  const int32_t *rowptr, *ent, *tab;
+  float* part;  // (2 nwin, F) chunk partials
+  float* dH;
+};
+
+// the Pk<T>::V fp32 elements from p (16 or 32 bytes)
+template <typename T>
+__device__ __forceinline__ Pk<T> pk_load_f32(const float* p) {
+  Pk<T> r;
+#pragma unroll
+  for (int i = 0; i < Pk<T>::V; i += 4) {
+    const float4 x = *reinterpret_cast<const float4*>(p + i);
+    r.v[i] = x.x; r.v[i + 1] = x.y; r.v[i + 2] = x.z; r.v[i + 3] = x.w;
+  }
+  return r;
+}
+
+// pg_sum_range with two gathered rows per endpoint: the loads of UNROLL endpoints' dx and h
+// pieces are issued before the first fma
+template <typename T>
+__device__ __forceinline__ Pk<T> pgv_sum_range(const PgVecArgs<T>& a, int beg, int end) {
+  constexpr int V = Pk<T>::V;
+  constexpr int UNROLL = 4;
+  const int lane = lane_id();
+  const int QP = a.F / V, EPW = kWave / QP;
+  const int slot = lane / QP, q = lane % QP;
+  Pk<T> acc = pk_zero<T>();
+  for (int base = beg; base < end; base += kWave) {
+    const int pos = base + lane;
+    int64_t pair = -1, other = 0;
+    if (pos < end) {
+      const int64_t e = a.ent[pos];
+      if ((uint64_t)e < (uint64_t)(2 * a.P)) {
+        const int64_t p = e < a.P ? e : e - a.P;
+        const int64_t o = e < a.P ? a.dst[p] : a.src[p];
+        if ((uint64_t)o < (uint64_t)a.n) {  // (a plan of another pair list: no stray read)
+          other = o;
+          pair = p;
+        }
+      }
+    }
+    const int cnt = min(kWave, end - base);
+    for (int j0 = 0; j0 < cnt; j0 += EPW * UNROLL) {
+      Pk<T> fac[UNROLL], row[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int j = j0 + u * EPW + slot;
+        const int64_t pv = __shfl(pair, j & (kWave - 1));
+        const int64_t ov = __shfl(other, j & (kWave - 1));
+        const bool on = j < cnt && pv >= 0;
+        fac[u] = on ? pk_load_f32<T>(a.dx + pv * a.F + V * q) : pk_zero<T>();
+        row[u] = on ? pk_load(a.h + ov * a.ld + V * q) : pk_zero<T>();
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+        for (int i = 0; i < V; ++i) acc.v[i] = fmaf(fac[u].v[i], row[u].v[i], acc.v[i]);
+    }
+  }
+  for (int o = QP; o < kWave; o <<= 1) acc = pk_xor_add(acc, o);
+  return acc;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kPgThreads) pgv_rows_kernel(PgVecArgs<T> a) {
+  constexpr int V = Pk<T>::V;
+  const int lane = lane_id();
+  const int QP = a.F / V;
+  const int64_t wave = ((int64_t)blockIdx.x * kPgThreads + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * kPgThreads) >> 6;
+  for (int64_t r = wave; r < a.n; r += nwaves) {
+    int b = a.rowptr[r], e = a.rowptr[r + 1];
+    if (b < 0 || e < b || (int64_t)e > 2 * a.P) b = e = 0;  // (not a plan of this list)
+    const bool lng = e - b > kPgChunk;
+    const Pk<T> acc = pgv_sum_range(a, b, lng ? b + kPgChunk : e);
+    float* out = lng ? a.part + (int64_t)(2 * (b / kPgChunk) + 1) * a.F : a.dH + r * a.F;
+    if (lane < QP) pg_store(out, acc, lane);
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kPgThreads) pgv_chunks_kernel(PgVecArgs<T> a, int64_t nwin) {
+  constexpr int V = Pk<T>::V;
+  const int lane = lane_id();
+  const int QP = a.F / V;
+  const int64_t wave = ((int64_t)blockIdx.x * kPgThreads + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * kPgThreads) >> 6;
+  for (int64_t m = wave; m < nwin; m += nwaves) {
+    const int64_t r = a.tab[2 * m];
+    const int b = a.tab[2 * m + 1];
+    if ((uint64_t)r >= (uint64_t)a.n || b < 0 || b / kPgChunk != m) continue;
+    const int e = min(b + kPgChunk, a.rowptr[r + 1]);
+    if ((int64_t)e > 2 * a.P) continue;  // (not a plan of this list)
+    const Pk<T> acc = pgv_sum_range(a, b, e);
+    if (lane < QP) pg_store(a.part + 2 * m * a.F, acc, lane);
+  }
+}
+
+template <typename T>
+static void pgv_launch(const PgVecArgs<T>& a, int64_t nwin, hipStream_t s) {
+  hipLaunchKernelGGL((pgv_rows_kernel<T>), dim3(grid_for(a.n, kPgWaves, 1 << 20)),
+                     dim3(kPgThreads), 0, s, a);
+  hipLaunchKernelGGL((pgv_chunks_kernel<T>), dim3(grid_for(nwin, kPgWaves, 1 << 20)),
+                     dim3(kPgThreads), 0, s, a, nwin);
+  hipLaunchKernelGGL(pg_finish_kernel, dim3(grid_for(a.n, kPgWaves, 1 << 16)), dim3(kPgThreads),
+                     0, s, a.P, a.n, a.F, a.rowptr, a.part, a.dH);
+}
+
 template <typename T, typename G>
 static void pg_launch(const PgArgs<T, G>& a, int64_t nwin, hipStream_t s) {
   hipLaunchKernelGGL((pg_rows_kernel<T, G>), dim3(grid_for(a.n, kPgWaves, 1 << 20)),

@@ -1642,6 +1642,149 @@ def link_bce_loss(h, src, dst, target, weight=None, plan=None, return_logits=Fal
     return (loss, z) if return_logits else loss
 
 
+class _LinkMLP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, W, b, src, dst, label, teacher, w_label, w_mse, p, seed, plan):
+        dt = h.dtype
+        hh = h.detach()
+        esz = hh.element_size()
+        if not (hh.stride(1) == 1 and (hh.stride(0) * esz) % 16 == 0 and hh.data_ptr() % 16 == 0):
+            hh = hh.contiguous()
+        n, Fd = hh.shape
+        N = W.shape[0]
+        Wk = _tc(W.detach(), dt)  # the kernel's weight: bf16 for a bf16 table (score_pairs)
+        bk = _f32c(b.detach())
+        P, dev = src.numel(), hh.device
+        out = torch.empty(P, N, dtype=torch.float32, device=dev)
+        terms = torch.empty(3, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)  # written by the kernel: no copy
+        pv = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = _workspace(dev, _lib.fn("msha_link_mlp_loss_fwd_workspace_size")(P))
+        _lib.call("msha_link_mlp_loss_fwd", P, Fd, N, _code(dt), hh.data_ptr(), hh.stride(0), n,
+                  src.data_ptr(), dst.data_ptr(), _lib.ptr(label), Wk.data_ptr(), bk.data_ptr(),
+                  _lib.ptr(teacher), w_label, w_mse, p, seed, 0, out.data_ptr(),
+                  terms.data_ptr(), loss.data_ptr(), pv.data_ptr(), ws.data_ptr(), ws.numel(),
+                  _stream(hh))
+        ctx.plan, ctx.dt, ctx.cfg = plan, dt, (w_label, w_mse, p)
+        ctx.wdt, ctx.bdt = W.dtype, b.dtype
+        ctx.save_for_backward(hh, Wk, src, dst, label, teacher, out, pv)
+        ctx.mark_non_differentiable(out, terms, pv)
+        return loss, out, terms, pv
+
+    @staticmethod
+    def backward(ctx, gloss, _go=None, _gt=None, _gp=None):
+        hh, Wk, src, dst, label, teacher, out, pv = ctx.saved_tensors
+        n, Fd = hh.shape
+        P, N = out.shape
+        dev, plan = hh.device, ctx.plan
+        w_label, w_mse, p = ctx.cfg
+        need_h, need_w = ctx.needs_input_grad[0], (ctx.needs_input_grad[1]
+                                                   or ctx.needs_input_grad[2])
+        g = gloss.detach().to(torch.float32).reshape(1).contiguous()
+        dz = torch.empty(P, N, dtype=torch.float32, device=dev)
+        dx = dH = dW = db = W32 = None
+        if need_h:
+            if plan is None:
+                raise RuntimeError("link_mlp_loss: the gradient to h needs a PairPlan (h did not "
+                                   "require grad when the loss was taken)")
+            dx = torch.empty(P, Fd, dtype=torch.float32, device=dev)  # the one (P, F) buffer
+            dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
+            W32 = _f32c(Wk)
+        if need_w:
+            dW = torch.empty(N, Fd, dtype=torch.float32, device=dev)
+            db = torch.empty(N, dtype=torch.float32, device=dev)
+        ws = _workspace(dev, _lib.fn("msha_link_mlp_bwd_workspace_size")(P, Fd, N))
+        _lib.call("msha_link_mlp_bwd", P, Fd, N, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n,
+                  src.data_ptr(), dst.data_ptr(), _lib.ptr(label), _lib.ptr(W32),
+                  _lib.ptr(teacher), out.data_ptr(), pv.data_ptr(), w_label, w_mse, p,
+                  g.data_ptr(), _lib.ptr(plan.rowptr if need_h else None),
+                  _lib.ptr(plan.ent if need_h else None),
+                  _lib.ptr(plan.chunk_tab if need_h else None), dz.data_ptr(), _lib.ptr(dx),
+                  _lib.ptr(dW), _lib.ptr(db), _lib.ptr(dH), ws.data_ptr(), ws.numel(),
+                  _stream(hh))
+        if need_h and ctx.dt != torch.float32:
+            dH = dH.to(ctx.dt)
+        if need_w:
+            dW = dW if ctx.wdt == torch.float32 else dW.to(ctx.wdt)
+            db = db if ctx.bdt == torch.float32 else db.to(ctx.bdt)
+        return (dH, dW if ctx.needs_input_grad[1] else None,
+                db if ctx.needs_input_grad[2] else None) + (None,) * 9
+
+
+def link_mlp_loss(h, src, dst, W, b, *, label=None, teacher_out=None, w_label=1.0, w_mse=0.0,
+                  p=0.0, training=False, seed=None, plan=None, return_output=False):
+    """LLP's training objective for the 'mlp' link predictor with one used Linear
+    (LLP.py:233, :235, :238), fused with the caller's gather:
+
+        out  = torch.sigmoid(F.dropout(F.relu(F.linear(h[src] * h[dst], W, b)), p, training))
+        loss = w_label * F.nll_loss(out, label) + w_mse * F.mse_loss(out, teacher_out)
+
+    ``h`` (n, F) float32 or bfloat16, ``W`` (N, F), ``b`` (N,), F and N powers of two in
+    [16, 128]; ``src`` / ``dst`` int64 (P,); ``label`` int64 (P,), default ``dst`` itself as
+    LLP.py:235 uses it; ``teacher_out`` (P, N), detached, or None (no MSE term).  A pair whose
+    ``src`` or ``dst`` lies outside [0, n) or whose label lies outside [0, N) is padding: it
+    adds nothing to any term or gradient and is not counted in the means (``out`` shows NaN
+    for it); with no valid pair the loss and every gradient are zero.  A bf16 ``h`` runs the
+    bf16 MFMA forward with ``W`` cast to bf16, as ``score_pairs`` does.  Dropout follows
+    ``msha_pair_linear``'s Philox stream (``dropout_keep_mask(P * N, p, seed)``).
+
+    Returns the fp32 scalar, or ``(loss, out, terms)`` with ``return_output``: ``out`` (P, N)
+    fp32 and ``terms`` = (loss, nll term, mse term), both without gradient.
+
+    Gradients go to ``h``, ``W`` and ``b`` in their own dtypes.  The only (P, F)-sized array
+    ever made is ``dx = dz @ W``; the weight gradient gathers ``h[src] * h[dst]`` in its MFMA
+    loader, and the table gradient is summed per row in the order of ``plan``
+    (``pair_plan(src, dst, n)``, built here when None and ``h`` needs a gradient; reuse it
+    for as long as the pair list is unchanged).  No float atomics: bitwise reproducible.
+    Nothing is read back, so plan + loss + backward can be captured into one HIP graph."""
+    if h.dtype not in (torch.float32, BF16):
+        raise TypeError(f"link_mlp_loss takes a float32 or bfloat16 table, got {h.dtype}")
+    if h.dim() != 2:
+        raise ValueError(f"link_mlp_loss: h must be (n, F), got {tuple(h.shape)}")
+    _pair_lists(src, dst, "link_mlp_loss")
+    P, Fd = src.numel(), h.shape[1]
+    if P < 1 or h.shape[0] < 1:
+        raise ValueError("link_mlp_loss: needs at least one pair and one table row")
+    if not W.is_floating_point() or W.dim() != 2 or W.shape[1] != Fd:
+        raise ValueError(f"link_mlp_loss: W must be a float (N, {Fd}) weight, got {W.dtype} "
+                         f"{tuple(W.shape)}")
+    N = W.shape[0]
+    if not b.is_floating_point() or b.shape != (N,):
+        raise ValueError(f"link_mlp_loss: b must be a float tensor of shape ({N},), got "
+                         f"{b.dtype} {tuple(b.shape)}")
+    if label is not None and (label.dtype != torch.int64 or label.shape != (P,)):
+        raise ValueError(f"link_mlp_loss: label must be an int64 tensor of shape ({P},), got "
+                         f"{label.dtype} {tuple(label.shape)}")
+    if teacher_out is not None and (not teacher_out.is_floating_point()
+                                    or teacher_out.shape != (P, N)):
+        raise ValueError(f"link_mlp_loss: teacher_out must be a float tensor of shape "
+                         f"({P}, {N}), got {teacher_out.dtype} {tuple(teacher_out.shape)}")
+    p = float(p) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"link_mlp_loss: p must be in [0, 1), got {p}")
+    if plan is not None and (not isinstance(plan, PairPlan) or plan.n != h.shape[0]
+                             or plan.n_pairs != P):
+        raise ValueError("link_mlp_loss: plan is not a PairPlan of this pair list and table")
+    if not _lib.fn("msha_link_mlp_supported")(Fd, N, _code(h.dtype)):
+        raise ValueError(f"link_mlp_loss: widths F = {Fd}, N = {N} of a {h.dtype} table are not "
+                         f"supported (powers of two in [16, 128])")
+    for t in (src, dst, W, b, label, teacher_out):
+        if t is not None and t.device != h.device:
+            raise ValueError("link_mlp_loss: every tensor must be on the table's device")
+    _lib.require_cuda(h)
+    src, dst = src.contiguous(), dst.contiguous()
+    label = label.contiguous() if label is not None else None
+    if teacher_out is not None:
+        teacher_out = teacher_out.detach().to(torch.float32).contiguous()
+    if seed is None:
+        seed = new_seed() if p > 0 else 0
+    if plan is None and h.requires_grad and torch.is_grad_enabled():
+        plan = pair_plan(src, dst, h.shape[0])  # only a backward reads it
+    loss, out, terms, _ = _LinkMLP.apply(h, W, b, src, dst, label, teacher_out, float(w_label),
+                                         float(w_mse), p, int(seed), plan)
+    return (loss, out, terms) if return_output else loss
+
+
 # ------------------------------------------------- link-prediction distillation ---
 MAX_CONTEXT = 64  # context slots per anchor (one lane each)
 

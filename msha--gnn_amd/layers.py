@@ -438,6 +438,27 @@ class LinkPredictor(torch.nn.Module):
         return MF.link_distill_loss(h, anchors, context, teacher_logits=teacher_logits,
                                     teacher_table=teacher_h, **kw)
 
+    def llp_loss(self, h, src, dst, teacher_out=None, label=None, true_label=10.0, kd_p=100.0,
+                 plan=None):
+        """LLP's objective for the 'mlp' predictor (LLP.py:233, :235, :238) with the
+        caller's gather fused: ``true_label * F.nll_loss(out, label) + kd_p *
+        F.mse_loss(out, teacher_out)`` of ``out = self(h[src], h[dst])``, ``label`` defaulting
+        to ``dst`` as the reference uses it (``functional.link_mlp_loss``: deterministic
+        gradients to ``h`` and to the first Linear).  The defaults are LLP.py's
+        ``--True_label`` and ``--KD_p``.  'mlp' with one used Linear only (the reference's
+        ``num_layers = 2``): a deeper head is not covered by the fused loss."""
+        if self.predictor != "mlp":
+            raise ValueError(f"LinkPredictor.llp_loss needs the 'mlp' predictor, got "
+                             f"{self.predictor!r}: the 'inner' objective is LinkPredictor.loss / "
+                             f".distill_loss")
+        if len(self.lins) != 2:
+            raise ValueError(f"LinkPredictor.llp_loss covers one used Linear (num_layers = 2, "
+                             f"LLP.py's default); this head applies {len(self.lins) - 1}: a "
+                             f"deeper head is out of scope of the fused loss")
+        return MF.link_mlp_loss(h, src, dst, self.lins[0].weight, self.lins[0].bias, label=label,
+                                teacher_out=teacher_out, w_label=true_label, w_mse=kd_p,
+                                p=self.dropout, training=self.training, plan=plan)
+
     def match_loss(self, h, rows, teacher_h):
         """LLP's representation-matching term ``KD_cosine(h[rows], teacher_h[rows])``
         (LLP.py:34-35, :237; ``functional.link_match_loss``: a histogram of ``rows`` and one
