@@ -1293,6 +1293,49 @@ MSHA_API int msha_link_mlp_bwd(int64_t n_pairs, int32_t feat, int32_t hidden, in
                                float* dx, float* dW, float* db, float* dH, void* ws,
                                size_t ws_bytes, msha_stream_t stream); /* (ABI 16, added) */
 
+/* ---- The GraphSAGE baseline on sparse adjacency rows (SGAE.py:41-56) (ABI 16, added) ------
+ *   x = table[src]  (B, in);  z1 = relu(x W1^T + b1)  (B, M);  y = adj[src] * z1  (hidden == M);
+ *   z2 = relu(y W2^T + b2)  (B, out);  logp = log_softmax(z2, dim = 1)
+ * with adj given by the graph's CSR (M = g->n_cols, table rows n = g->n_rows) and vals, the
+ * fp32 adjacency value of every CSR edge: y_j is zero off the row's edges, so both Linears run
+ * over the edges of row src_b alone, deg (in + out) multiply-adds an entry.  Only edges with
+ * adj > 0 are in a graph: negative adjacency entries are not supported.  table (n, in) fp32
+ * with row pitch ld elements; W1 (M, in), b1 (M), W2 (out, M), b2 (out) fp32, contiguous; in,
+ * M and out each 16, 32 or 64 (msha_sage_supported).  src int64 (B), 0 <= B < 2^30.  An entry
+ * whose source is outside [0, n) is padding: its logp row is NaN and it enters no gradient,
+ * decided before any load through it.  A virtual row (rowflag set) is skipped: y = 0, logp =
+ * log_softmax(relu(b2)), as for a real row whose values are all 0.  A CSR row longer than M
+ * (repeated columns) is treated as empty.
+ * Forward: one launch, 16 lanes an entry, the parameters staged in LDS, p2 in registers;
+ * logp (B, out) fp32 is the only output and nothing else is kept. */
+MSHA_API int msha_sage_supported(int32_t in, int32_t M, int32_t out); /* host-only (ABI 16, added) */
+MSHA_API int msha_sage_fwd(const msha_graph* g, int64_t B, const int64_t* src, int32_t in,
+                           int32_t out, const float* table, int64_t ld, const float* vals,
+                           const float* W1, const float* b1, const float* W2, const float* b2,
+                           float* logp, msha_stream_t stream); /* (ABI 16, added) */
+/* Its backward for a general upstream dlogp (B, out) (ABI 16, added), from the forward's logp:
+ *   rows    the entry recomputed (the same arithmetic, so the same ReLU branches),
+ *           dr = (dlogp - exp(logp) sum_o dlogp) [p2 > 0]; per edge dy_j = W2[:, j] . dr,
+ *           dz1_j = a dy_j [p1_j > 0], dx_b += dz1_j W1[j, :]
+ *   wgrad   dW1[j, :] += dz1_j x_b, db1[j] += dz1_j, dW2[:, j] += y_j dr, db2 += dr in LDS
+ *           accumulators with one writing wave each, batch order; blocks own runs of entries
+ *           (at most 512 blocks, a function of B alone) and their partials are added in a
+ *           fixed order.  dW1, db1, dW2, db2: all four or none (NULL: skipped).
+ *   table   dS (n, in) fp32, contiguous, 16-byte aligned, nullable: dS[r] = the dx rows of the
+ *           entries with src_b = r added in batch order under msha_pair_plan(src, src); every
+ *           row is written, exact zeros outside the batch.
+ * No float atomics: every output is a function of the inputs alone, bitwise reproducible.
+ * Nothing is read back or allocated: capturable.  ws: msha_sage_workspace_size bytes,
+ * 16-byte aligned (n = g->n_rows).  B = 0 writes zeros. */
+MSHA_API size_t msha_sage_workspace_size(int64_t B, int64_t n, int32_t in, int32_t M,
+                                         int32_t out); /* (ABI 16, added) */
+MSHA_API int msha_sage_bwd(const msha_graph* g, int64_t B, const int64_t* src, int32_t in,
+                           int32_t out, const float* table, int64_t ld, const float* vals,
+                           const float* W1, const float* b1, const float* W2, const float* b2,
+                           const float* logp, const float* dlogp, float* dS, float* dW1,
+                           float* db1, float* dW2, float* db2, void* ws, size_t ws_bytes,
+                           msha_stream_t stream); /* (ABI 16, added) */
+
 #ifdef __cplusplus
 }
 #endif

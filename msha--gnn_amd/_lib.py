@@ -283,6 +283,12 @@ SIGNATURES = {
     "msha_link_mlp_bwd_workspace_size": (SZ, [I64, I32, I32]),
     "msha_link_mlp_bwd": (C.c_int, [I64, I32, I32, I32, P, I64, I64, P, P, P, P, P, P, P, F32, F32,
                                     F32, P, P, P, P, P, P, P, P, P, P, SZ, P]),
+    # GraphSAGE baseline on sparse adjacency rows (ABI 16, added)
+    "msha_sage_supported": (C.c_int, [I32, I32, I32]),
+    "msha_sage_workspace_size": (SZ, [I64, I64, I32, I32, I32]),
+    "msha_sage_fwd": (C.c_int, [GP, I64, P, I32, I32, P, I64, P, P, P, P, P, P, P]),
+    "msha_sage_bwd": (C.c_int, [GP, I64, P, I32, I32, P, I64, P, P, P, P, P, P, P, P, P, P, P,
+                                P, P, SZ, P]),
 }
 
 _lib = None

@@ -823,6 +823,126 @@ def spmm(graph: Graph, vals: torch.Tensor, table: torch.Tensor, transpose: bool 
     return _SpMM.apply(table, vals, graph, transpose)
 
 
+# ------------------------------------------ GraphSAGE baseline (SGAE.py:41-56) ---
+SAGE_WIDTHS = (16, 32, 64)  # in, M = hidden and out of msha_sage_fwd (msha_sage_supported)
+
+
+def _sage_fwd(tb, src, graph, vals, W1, b1, W2, b2):
+    B, out = src.numel(), W2.shape[0]
+    logp = torch.empty(B, out, dtype=torch.float32, device=tb.device)
+    _lib.call("msha_sage_fwd", graph.desc, B, src.data_ptr(), tb.shape[1], out, tb.data_ptr(),
+              tb.stride(0), vals.data_ptr(), W1.data_ptr(), b1.data_ptr(), W2.data_ptr(),
+              b2.data_ptr(), logp.data_ptr(), _stream(tb))
+    return logp
+
+
+class _Sage(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, W1, b1, W2, b2, src, graph, vals):
+        tb = table.detach()
+        if tb.stride(1) != 1:
+            tb = tb.contiguous()
+        W1, b1, W2, b2 = (t.detach().contiguous() for t in (W1, b1, W2, b2))
+        logp = _sage_fwd(tb, src, graph, vals, W1, b1, W2, b2)
+        ctx.graph = graph
+        ctx.save_for_backward(tb, W1, b1, W2, b2, src, vals, logp)
+        return logp
+
+    @staticmethod
+    def backward(ctx, dlogp):
+        tb, W1, b1, W2, b2, src, vals, logp = ctx.saved_tensors
+        g = ctx.graph
+        n, in_f = tb.shape
+        B, out = logp.shape
+        dev = tb.device
+        need_t, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:5])
+        dl = dlogp.detach().to(torch.float32).contiguous()
+        dS = dW1 = db1 = dW2 = db2 = None
+        if need_t:
+            dS = torch.empty(n, in_f, dtype=torch.float32, device=dev)
+        if need_w:
+            dW1, db1, dW2, db2 = (torch.empty_like(t) for t in (W1, b1, W2, b2))
+        ws = _workspace(dev, _lib.fn("msha_sage_workspace_size")(B, n, in_f, g.n_cols, out))
+        _lib.call("msha_sage_bwd", g.desc, B, src.data_ptr(), in_f, out, tb.data_ptr(),
+                  tb.stride(0), vals.data_ptr(), W1.data_ptr(), b1.data_ptr(), W2.data_ptr(),
+                  b2.data_ptr(), logp.data_ptr(), dl.data_ptr(), _lib.ptr(dS), _lib.ptr(dW1),
+                  _lib.ptr(db1), _lib.ptr(dW2), _lib.ptr(db2), ws.data_ptr(), ws.numel(),
+                  _stream(tb))
+        need = ctx.needs_input_grad
+        return (dS, dW1 if need[1] else None, db1 if need[2] else None,
+                dW2 if need[3] else None, db2 if need[4] else None, None, None, None)
+
+
+def sage_forward(table, src, graph, vals, W1, b1, W2, b2, check=True):
+    """The GraphSAGE baseline of SGAE.py:41-56 on the sparse rows of the adjacency:
+
+        x = table[src];  z1 = relu(x W1^T + b1);  y = adj[src] * z1
+        logp = log_softmax(relu(y W2^T + b2), dim=1)                     (B, out)
+
+    with ``adj`` given as its ``Graph`` (``graph_of(adj)``) and the fp32 values of its CSR
+    edges (``graph.values(adj)``).  ``y`` is zero off the edges of row ``src_b``, so both
+    Linears run over that row's edges alone and no dense ``adj[src]`` is read.  Only entries
+    with ``adj > 0`` are edges: negative adjacency values are not supported.  ``table``
+    (n, in), ``W1`` (M, in), ``b1`` (M,), ``W2`` (out, M), ``b2`` (out,) float32 with in, M
+    and out each in ``SAGE_WIDTHS``; ``graph`` over (n, M) (SGAE.py:54 multiplies elementwise:
+    hidden == M); ``src`` int64 (B,), B >= 0.
+
+    ``check`` (default) applies torch's ``table[src]`` rule first (``check_pair_indices``:
+    IndexError outside [-n, n), negative indices wrapped; one stream sync).  With
+    ``check=False`` the caller vouches for indices in [0, n) -- as inside a captured HIP
+    graph, where nothing may be read back; the kernels still bound every index and give a
+    stray entry a NaN row and no gradient.
+
+    Gradients go to ``table``, ``W1``, ``b1``, ``W2`` and ``b2`` for any upstream gradient.
+    The forward keeps only its output; the backward recomputes the entry.  No float atomics:
+    the weight gradients are block partials added in a fixed order, the table gradient adds the
+    entries of a row in batch order (exact zeros for rows outside the batch), so every
+    result is bitwise reproducible.  Nothing is read back with ``check=False``."""
+    for name, t in (("table", table), ("W1", W1), ("b1", b1), ("W2", W2), ("b2", b2),
+                    ("vals", vals)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"sage_forward: {name} must be float32, got {t.dtype}")
+    if not isinstance(graph, Graph):
+        raise TypeError("sage_forward takes the adjacency's Graph and its edge values "
+                        "(graph_of(adj), graph.values(adj))")
+    if src.dtype != torch.int64 or src.dim() != 1:
+        raise ValueError(f"sage_forward: src must be a 1-D int64 tensor, got {src.dtype} "
+                         f"{tuple(src.shape)}")
+    if table.dim() != 2 or W1.dim() != 2 or W2.dim() != 2:
+        raise ValueError(f"sage_forward: table {tuple(table.shape)}, W1 {tuple(W1.shape)} and "
+                         f"W2 {tuple(W2.shape)} must be 2-D")
+    if graph.n_rows != table.shape[0]:
+        raise ValueError(f"sage_forward: the graph has {graph.n_rows} rows, the table "
+                         f"{table.shape[0]}")
+    if not (W1.shape[0] == graph.n_cols == W2.shape[1]):
+        raise ValueError(f"sage_forward: hidden = {W1.shape[0]} (W1), {W2.shape[1]} (W2) and "
+                         f"the adjacency's {graph.n_cols} columns must be equal: SGAE.py:54 "
+                         f"multiplies adj[source_index] and the hidden layer elementwise")
+    in_f, M, out = table.shape[1], graph.n_cols, W2.shape[0]
+    if not all(w in SAGE_WIDTHS for w in (in_f, M, out)):
+        raise ValueError(f"sage_forward: widths in = {in_f}, hidden = {M}, out = {out} are not "
+                         f"supported: each must be one of {SAGE_WIDTHS}")
+    if W1.shape[1] != in_f or b1.shape != (M,) or b2.shape != (out,):
+        raise ValueError(f"sage_forward: W1 {tuple(W1.shape)}, b1 {tuple(b1.shape)}, b2 "
+                         f"{tuple(b2.shape)} do not fit in = {in_f}, hidden = {M}, out = {out}")
+    if vals.shape != (graph.n_edges,) or vals.requires_grad:
+        raise ValueError(f"sage_forward: vals must be the {graph.n_edges} edge values of the "
+                         f"graph, without gradient (graph.values(adj))")
+    if not graph.distinct_cols:
+        raise ValueError("sage_forward: the graph's rows must have distinct columns")
+    _lib.require_cuda(table, src, vals, W1, b1, W2, b2)
+    src = src.contiguous()
+    if check and src.numel():
+        src, _ = check_pair_indices(src, src, table.shape[0])
+    vals = vals.contiguous()
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (table, W1, b1, W2, b2)):
+        return _Sage.apply(table, W1, b1, W2, b2, src, graph, vals)
+    tb = table.detach()
+    if tb.stride(1) != 1:
+        tb = tb.contiguous()
+    return _sage_fwd(tb, src, graph, vals, *(t.detach().contiguous() for t in (W1, b1, W2, b2)))
+
+
 # --------------------------------------------------- BatchNorm + LeakyReLU ---
 class _BnLRelu(torch.autograd.Function):
     """lrelu(batch_norm(x)) with training batch statistics (Ablation.py:273-274)."""

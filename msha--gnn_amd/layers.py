@@ -15,6 +15,8 @@ and RNG consumption order as the reference, so a model built after
   MLP                   LLP.py:36-84       (the student encoder; norm_type 'none' only)
   OursLayer, Ours       Ours.py:29-167 (full MSHA: inter + city/province attention)
   GraphConvolution, GCN model.py:11-64     (SpMM over the same CSR/CSC machinery)
+  GraphSAGE             SGAE.py:41-56      (the baseline's two Linears on the adjacency's
+                                            sparse rows: forward(source_index, adj))
 
 Adjacency arguments may be dense (N, M) tensors (as in train.py; the CSR/CSC view
 is built once on the GPU and cached) or prebuilt ``Graph`` objects.  Every
@@ -749,3 +751,32 @@ class GCN(nn.Module):
         x = F.dropout(x, self.dropout, training=self.training)
         x = F.relu(self.gc2(x, adj.t()))
         return F.log_softmax(x, dim=1)
+
+
+class GraphSAGE(nn.Module):
+    """SGAE.py:41-56, the GraphSAGE baseline of the comparison table: ``Sfeatures`` (the
+    table with the GDP column, ``len(gdp)`` rows -- the reference's module global ``Scount``),
+    then ``linear1`` and ``linear2`` in the reference's init order.  ``forward(source_index,
+    adj)`` takes the dense (N, M) adjacency, hidden_features == M (SGAE.py:54 multiplies
+    elementwise), and runs ``functional.sage_forward`` on the adjacency's cached CSR and edge
+    values: one launch forward, no dense ``adj[source_index]``."""
+
+    def __init__(self, in_features, hidden_features, out_features, gdp):
+        super().__init__()
+        self.Sfeatures = _features_with_gdp(len(gdp), in_features, gdp)
+        self.linear1 = nn.Linear(in_features, hidden_features)
+        self.linear2 = nn.Linear(hidden_features, out_features)
+
+    def forward(self, source_index, adj):
+        if isinstance(adj, Graph):
+            raise TypeError("GraphSAGE needs the dense adjacency (its values weight the hidden "
+                            "layer)")
+        if adj.requires_grad:
+            raise ValueError("GraphSAGE: the adjacency is data, not a parameter "
+                             "(adj.requires_grad is set)")
+        g, transposed = graph_of(adj)
+        if transposed:
+            raise ValueError("GraphSAGE: pass the (N, M) adjacency itself, not a transposed view")
+        return MF.sage_forward(self.Sfeatures, source_index, g, g.values(adj),
+                               self.linear1.weight, self.linear1.bias, self.linear2.weight,
+                               self.linear2.bias)
