@@ -833,6 +833,21 @@ MSHA_API size_t msha_adam_workspace_size(void);
 MSHA_API int msha_adam_step(int32_t n, const msha_adam_tensor* tensors, double lr,
                             double beta1, double beta2, double eps, double weight_decay,
                             void* ws, msha_stream_t stream);
+/* The same update at weight_decay 0 for the rows of a touched-row list only (ABI 16, added):
+ * for i < n_rows[0] (a DEVICE count, at most cap) and r = rows[i], the rows param[r],
+ * exp_avg[r], exp_avg_sq[r] of an (n, feat) contiguous fp32 or bf16 table are updated from
+ * the gradient vals[i] ((cap, feat) fp32; for a bf16 table first rounded once to bf16, to
+ * nearest even, as the dense path's cast does) with the scalars of t = *step + 1; then *step
+ * = t, by a trailing one-thread launch, so every row of one call sees one t.  One step count
+ * per table: a row's moments are not decayed in the steps that do not name it.  Rows outside
+ * the list are neither read nor written; a step that names every row leaves the bits of
+ * msha_adam_step.  rows must be distinct (msha_plan_rows); an entry outside [0, n) is skipped.
+ * feat as msha_link_bce_supported; 1 <= cap <= n; no float atomics. */
+MSHA_API int msha_adam_rows_step(int64_t n, int32_t feat, int32_t dtype, void* param,
+                                 void* exp_avg, void* exp_avg_sq, float* step,
+                                 const int32_t* rows, const int32_t* n_rows, int64_t cap,
+                                 const float* vals, double lr, double beta1, double beta2,
+                                 double eps, msha_stream_t stream); /* (ABI 16, added) */
 
 /* ---- Projection of a small node table in one workgroup (the recipient side: R15 has 32
  * recipients; Ablation.py:262, :266-267): h = X @ W (M x N, N = heads*feat) with optional
@@ -1136,6 +1151,31 @@ MSHA_API int msha_link_bce_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, con
                                const float* gloss, const int32_t* plan_rowptr,
                                const int32_t* plan_ent, const int32_t* plan_chunk_tab, float* dH,
                                void* ws, size_t ws_bytes, msha_stream_t stream);
+/* Touched-row list of a plan (ABI 16, added): rows int32, capacity cap = min(n, 2 n_pairs),
+ * the ascending ids of the table rows r with rowptr[r + 1] > rowptr[r]; entries past the count
+ * are -1; n_rows[0] the count, a DEVICE int32.  Flag, exclusive scan, compact: integer work,
+ * no atomics, nothing read back, a pure function of the plan.  Padding pairs are in no row
+ * and touch none.  A row whose rowptr pair is not a plan's (negative, decreasing, past
+ * 2 n_pairs) is empty, as the gradient reads it; the list never passes cap.  rows may be
+ * NULL when cap is 0.  ws: msha_plan_rows_workspace_size(n) bytes, 16-byte aligned. */
+MSHA_API size_t msha_plan_rows_workspace_size(int64_t n); /* (ABI 16, added) */
+MSHA_API int msha_plan_rows(int64_t n, int64_t n_pairs, const int32_t* plan_rowptr, int32_t* rows,
+                            int32_t* n_rows, void* ws, size_t ws_bytes,
+                            msha_stream_t stream); /* (ABI 16, added) */
+/* msha_link_bce_bwd for the rows of the list only (ABI 16, added): vals (cap, feat) fp32,
+ * vals[i] bit for bit what msha_link_bce_bwd writes to dH[rows[i]] (the same per-row sum, the
+ * same chunk partials and chunk-order finish) for i < n_rows[0], zeros from there to cap.
+ * The loops run to the list's DEVICE count and capacity, never to n: the cost is the touched
+ * rows'.  cap must be min(n, 2 n_pairs); rows, n_rows from msha_plan_rows of the same plan.
+ * ws: msha_link_bce_bwd_workspace_size bytes. */
+MSHA_API int msha_link_bce_bwd_rows(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
+                                    int64_t ld, int64_t n, const int64_t* src, const int64_t* dst,
+                                    const float* target, const float* weight, const float* z,
+                                    const float* gloss, const int32_t* plan_rowptr,
+                                    const int32_t* plan_ent, const int32_t* plan_chunk_tab,
+                                    const int32_t* rows, const int32_t* n_rows, int64_t cap,
+                                    float* vals, void* ws, size_t ws_bytes,
+                                    msha_stream_t stream); /* (ABI 16, added) */
 
 /* ---- Link-prediction distillation for the inner-product scorer (LLP.py:231-238: a
  * teacher-matching term added to the label loss) (ABI 16, added) ------------------------
@@ -1193,6 +1233,15 @@ MSHA_API int msha_pair_grad_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, co
                                 const float* g, const float* gloss, const int32_t* plan_rowptr,
                                 const int32_t* plan_ent, const int32_t* plan_chunk_tab, float* dH,
                                 void* ws, size_t ws_bytes, msha_stream_t stream); /* (ABI 16, added) */
+/* msha_pair_grad_bwd for the rows of a touched-row list only (ABI 16, added): vals, rows,
+ * n_rows and cap exactly as msha_link_bce_bwd_rows. */
+MSHA_API int msha_pair_grad_bwd_rows(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
+                                     int64_t ld, int64_t n, const int64_t* src,
+                                     const int64_t* dst, const float* g, const float* gloss,
+                                     const int32_t* plan_rowptr, const int32_t* plan_ent,
+                                     const int32_t* plan_chunk_tab, const int32_t* rows,
+                                     const int32_t* n_rows, int64_t cap, float* vals, void* ws,
+                                     size_t ws_bytes, msha_stream_t stream); /* (ABI 16, added) */
 
 /* ---- Representation matching (LLP.py:34-35, :237: KD_cosine(h[rows], t_h[rows]) added to
  * the student's loss) (ABI 16, added) ---------------------------------------------------

@@ -283,6 +283,15 @@ SIGNATURES = {
     "msha_link_mlp_bwd_workspace_size": (SZ, [I64, I32, I32]),
     "msha_link_mlp_bwd": (C.c_int, [I64, I32, I32, I32, P, I64, I64, P, P, P, P, P, P, P, F32, F32,
                                     F32, P, P, P, P, P, P, P, P, P, P, SZ, P]),
+    # row-sparse table training: touched rows, compact gradient, lazy Adam (ABI 16, added)
+    "msha_plan_rows_workspace_size": (SZ, [I64]),
+    "msha_plan_rows": (C.c_int, [I64, I64, P, P, P, P, SZ, P]),
+    "msha_link_bce_bwd_rows": (C.c_int, [I64, I32, I32, P, I64, I64, P, P, P, P, P, P, P, P, P,
+                                         P, P, I64, P, P, SZ, P]),
+    "msha_pair_grad_bwd_rows": (C.c_int, [I64, I32, I32, P, I64, I64, P, P, P, P, P, P, P, P, P,
+                                          I64, P, P, SZ, P]),
+    "msha_adam_rows_step": (C.c_int, [I64, I32, I32, P, P, P, P, P, P, I64, P, C.c_double,
+                                      C.c_double, C.c_double, C.c_double, P]),
     # GraphSAGE baseline on sparse adjacency rows (ABI 16, added)
     "msha_sage_supported": (C.c_int, [I32, I32, I32]),
     "msha_sage_workspace_size": (SZ, [I64, I64, I32, I32, I32]),

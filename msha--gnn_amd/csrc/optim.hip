@@ -11,6 +11,7 @@
 // addcdiv with step_size = lr / bias_correction1), fp32 per element with the bias
 // corrections in double from the step count, as torch computes them on the host.
 #include "common.h"
+#include "pair_grad.h"  // pg_width_ok: the row widths of the link losses
 
 namespace msha {
 
@@ -68,8 +69,8 @@ __device__ __forceinline__ void adam_elem(const AdamScalars& a, float g, float& 
 
 // bias corrections of step t (exact integer t) in double, as torch computes them on the
 // host: beta ** t by squaring (<= 2 log2 t double multiplies, a few ulps)
-__device__ __forceinline__ float2 adam_scalars(const AdamBatch& b, float t) {
-  double p1 = 1.0, p2 = 1.0, s1 = b.b1, s2 = b.b2;
+__device__ __forceinline__ float2 adam_scalars(double lr, double b1, double b2, float t) {
+  double p1 = 1.0, p2 = 1.0, s1 = b1, s2 = b2;
   for (uint32_t e = (uint32_t)t; e != 0; e >>= 1) {
     if (e & 1u) {
       p1 *= s1;
@@ -78,7 +79,10 @@ __device__ __forceinline__ float2 adam_scalars(const AdamBatch& b, float t) {
     s1 *= s1;
     s2 *= s2;
   }
-  return make_float2((float)(b.lr / (1.0 - p1)), (float)sqrt(1.0 - p2));
+  return make_float2((float)(lr / (1.0 - p1)), (float)sqrt(1.0 - p2));
+}
+__device__ __forceinline__ float2 adam_scalars(const AdamBatch& b, float t) {
+  return adam_scalars(b.lr, b.b1, b.b2, t);
 }
 
 // One launch (round 5 ran a one-block launch ahead of the update for the scalars: one more
@@ -184,6 +188,96 @@ __global__ void __launch_bounds__(256) adam_kernel(AdamBatch b) {
   }
 }
 
+// ---- lazy Adam over the touched rows of a table (msha_adam_rows_step): the update above at
+// weight_decay 0, for the rows of a list (msha_plan_rows) only, the gradient of list entry i
+// in the fp32 row vals[i] (msha_link_bce_bwd_rows).  A lane group of F * esz / 16 lanes owns a
+// row, 16 bytes of every operand per lane; rows outside the list are neither read nor
+// written.  One step count for the whole table: every lane group reads it, and a trailing
+// one-thread launch advances it (stream order: after every read).
+struct AdamRows {
+  void *param, *exp_avg, *exp_avg_sq;
+  float* step;
+  const int32_t *rows, *n_rows;
+  const float* vals;
+  int64_t n, cap;
+  int F, dt;
+  double lr, b1, b2, eps;
+};
+
+// the gradient a bf16 table's dense path sees: the fp32 sum rounded once to bf16
+__device__ __forceinline__ float ad_round(int dt, float x) {
+  return dt == MSHA_DTYPE_BF16 ? (float)(bf16_t)x : x;
+}
+
+// 8 bf16 elements, one 16-byte piece (ad_ld4 / ad_st4 twice over, in one memory operation)
+__device__ __forceinline__ void ad_ld8(const void* p, int64_t q, float (&x)[8]) {
+  const uint4 w = reinterpret_cast<const uint4*>(p)[q];
+  const uint32_t u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    x[2 * k] = __uint_as_float(u[k] << 16);
+    x[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
+  }
+}
+__device__ __forceinline__ void ad_st8(void* p, int64_t q, const float (&x)[8]) {
+  reinterpret_cast<uint4*>(p)[q] = make_uint4(pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3]),
+                                              pack_bf16x2(x[4], x[5]), pack_bf16x2(x[6], x[7]));
+}
+
+__global__ void __launch_bounds__(256) adam_rows_kernel(AdamRows b) {
+  const int dt = b.dt;
+  const int np = dt == MSHA_DTYPE_BF16 ? 2 : 1;  // 4-element pieces in a lane's 16 bytes
+  const int F4 = b.F / 4, G = F4 / np;           // G: lanes per row, a power of two <= 64
+  const int64_t c = b.n_rows[0];
+  const int64_t cnt = c < 0 ? 0 : c > b.cap ? b.cap : c;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ngroups = (int64_t)gridDim.x * blockDim.x / G;
+  const int q = (int)(tid % G);
+  if (tid / G >= cnt) return;
+  const float2 sc = adam_scalars(b.lr, b.b1, b.b2, *b.step + 1.f);
+  AdamScalars a;
+  a.b1c = (float)(1.0 - b.b1);
+  a.b2c = (float)(1.0 - b.b2);
+  a.b2 = (float)b.b2;
+  a.wd = 0.f;
+  a.eps = (float)b.eps;
+  a.step_size = sc.x;
+  a.bc2_sqrt = sc.y;
+  const float4* vals = reinterpret_cast<const float4*>(b.vals);
+  for (int64_t i = tid / G; i < cnt; i += ngroups) {
+    const int64_t r = b.rows[i];
+    if ((uint64_t)r >= (uint64_t)b.n) continue;  // (not a list of this table: no stray access)
+    if (dt == MSHA_DTYPE_BF16) {  // 8 elements: one 16-byte piece of p, m, v, two of vals
+      const int64_t qt = r * G + q;
+      const float4 g0 = vals[i * F4 + 2 * q], g1 = vals[i * F4 + 2 * q + 1];
+      float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+      float p[8], m[8], v[8];
+      ad_ld8(b.param, qt, p);
+      ad_ld8(b.exp_avg, qt, m);
+      ad_ld8(b.exp_avg_sq, qt, v);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) adam_elem(a, ad_round(dt, g[k]), p[k], m[k], v[k]);
+      ad_st8(b.param, qt, p);
+      ad_st8(b.exp_avg, qt, m);
+      ad_st8(b.exp_avg_sq, qt, v);
+    } else {
+      const int64_t qt = r * F4 + q;
+      const float4 g = vals[i * F4 + q];
+      float4 p = ad_ld4(b.param, dt, qt);
+      float4 m = ad_ld4(b.exp_avg, dt, qt), v = ad_ld4(b.exp_avg_sq, dt, qt);
+      adam_elem(a, g.x, p.x, m.x, v.x);
+      adam_elem(a, g.y, p.y, m.y, v.y);
+      adam_elem(a, g.z, p.z, m.z, v.z);
+      adam_elem(a, g.w, p.w, m.w, v.w);
+      ad_st4(b.param, dt, qt, p);
+      ad_st4(b.exp_avg, dt, qt, m);
+      ad_st4(b.exp_avg_sq, dt, qt, v);
+    }
+  }
+}
+
+__global__ void adam_rows_tick_kernel(float* step) { *step = *step + 1.f; }
+
 }  // namespace msha
 
 using namespace msha;
@@ -226,6 +320,37 @@ extern "C" int msha_adam_step(int32_t n, const msha_adam_tensor* tensors, double
   b.ticket = (uint32_t*)ws;
   hipLaunchKernelGGL(adam_kernel, dim3(nblocks), dim3(256), 0, s, b);
   return check_launch("adam_step");
+}
+
+extern "C" int msha_adam_rows_step(int64_t n, int32_t feat, int32_t dtype, void* param,
+                                   void* exp_avg, void* exp_avg_sq, float* step,
+                                   const int32_t* rows, const int32_t* n_rows, int64_t cap,
+                                   const float* vals, double lr, double beta1, double beta2,
+                                   double eps, msha_stream_t stream) {
+  MSHA_ARG_CHECK(n >= 1 && n < ((int64_t)1 << 31) - 1,
+                 "adam_rows_step: bad sizes (1 <= n < 2^31 - 1)");
+  MSHA_ARG_CHECK(pg_width_ok(feat, dtype),
+                 "adam_rows_step: unsupported width: feat must be a power of two in [16 B, "
+                 "64 lanes x 16 B] of an fp32 or bf16 table (msha_link_bce_supported)");
+  MSHA_ARG_CHECK(cap >= 1 && cap <= n, "adam_rows_step: cap must be in [1, n] (msha_plan_rows)");
+  MSHA_ARG_CHECK(param && exp_avg && exp_avg_sq && step && rows && n_rows && vals,
+                 "adam_rows_step: null pointer");
+  MSHA_ARG_CHECK((((uintptr_t)param | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq |
+                   (uintptr_t)vals) & 15) == 0,
+                 "adam_rows_step: the table, its moments and vals must be 16-byte aligned");
+  MSHA_ARG_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
+                 "adam_rows_step: bad hyperparameters");
+  AdamRows b{};
+  b.param = param, b.exp_avg = exp_avg, b.exp_avg_sq = exp_avg_sq, b.step = step;
+  b.rows = rows, b.n_rows = n_rows, b.vals = vals;
+  b.n = n, b.cap = cap, b.F = feat, b.dt = dtype;
+  b.lr = lr, b.b1 = beta1, b.b2 = beta2, b.eps = eps;
+  const int lanes = feat * (dtype == MSHA_DTYPE_BF16 ? 2 : 4) / 16;  // per row
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(adam_rows_kernel, dim3(grid_for(cap, 256 / lanes, 1 << 20)), dim3(256), 0,
+                     s, b);
+  hipLaunchKernelGGL(adam_rows_tick_kernel, dim3(1), dim3(1), 0, s, step);
+  return check_launch("adam_rows_step");
 }
 
 extern "C" size_t msha_adam_workspace_size(void) {

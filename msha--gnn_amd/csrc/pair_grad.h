@@ -30,6 +30,32 @@ struct PgArgs {
   float* dH;
 };
 
+// Which rows a launch sums and where row i of its loop is written: every table row, row r
+// to dH[r] (PgAllRows), or the touched-row list of the plan (msha_plan_rows), row rows[i] to
+// vals[i] (PgListRows; the loop runs to the list's capacity, and an entry past the device
+// count, or one outside the table, is an empty row: zeros).  The sums themselves are shared.
+struct PgAllRows {
+  static constexpr const char* kOut = "dH";
+  __device__ __forceinline__ int64_t extent(int64_t n) const { return n; }
+  __device__ __forceinline__ int64_t count(int64_t n) const { return n; }
+  __device__ __forceinline__ int64_t row(int64_t i, int64_t) const { return i; }
+  int64_t grid_rows(int64_t n) const { return n; }
+};
+struct PgListRows {
+  static constexpr const char* kOut = "vals";
+  const int32_t *rows, *n_rows;
+  int64_t cap;
+  __device__ __forceinline__ int64_t extent(int64_t) const { return cap; }
+  __device__ __forceinline__ int64_t count(int64_t) const {
+    const int64_t c = n_rows[0];
+    return c < 0 ? 0 : c > cap ? cap : c;
+  }
+  __device__ __forceinline__ int64_t row(int64_t i, int64_t cnt) const {
+    return i < cnt ? (int64_t)rows[i] : -1;
+  }
+  int64_t grid_rows(int64_t) const { return cap; }
+};
+
 // sum over the endpoints ent[beg, end) of g h[other], one wave: 64 endpoints' scalars are
 // loaded a lane each, then their rows are gathered 64 / QP at a time (QP lanes x 16 bytes a
 // row).  Endpoint i of the range goes to lane group i % (64 / QP); the groups are added by an
@@ -90,19 +116,22 @@ __device__ __forceinline__ void pg_store(float* out, const Pk<T>& acc, int q) {
 
 // one wave per table row: its first min(deg, C) endpoints; a row of at most C endpoints is
 // complete (zeros for none), a longer one leaves its first chunk's partial
-template <typename T, typename G>
-__global__ void __launch_bounds__(kPgThreads) pg_rows_kernel(PgArgs<T, G> a) {
+template <typename T, typename G, typename R>
+__global__ void __launch_bounds__(kPgThreads) pg_rows_kernel(PgArgs<T, G> a, R rows) {
   constexpr int V = Pk<T>::V;
   const int lane = lane_id();
   const int QP = a.F / V;
   const int64_t wave = ((int64_t)blockIdx.x * kPgThreads + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * kPgThreads) >> 6;
-  for (int64_t r = wave; r < a.n; r += nwaves) {
-    int b = a.rowptr[r], e = a.rowptr[r + 1];
+  const int64_t cnt = rows.count(a.n), ext = rows.extent(a.n);
+  for (int64_t i = wave; i < ext; i += nwaves) {
+    const int64_t r = rows.row(i, cnt);
+    int b = 0, e = 0;
+    if ((uint64_t)r < (uint64_t)a.n) b = a.rowptr[r], e = a.rowptr[r + 1];
     if (b < 0 || e < b || (int64_t)e > 2 * a.P) b = e = 0;  // (not a plan of this list)
     const bool lng = e - b > kPgChunk;
     const Pk<T> acc = pg_sum_range(a, b, lng ? b + kPgChunk : e);
-    float* out = lng ? a.part + (int64_t)(2 * (b / kPgChunk) + 1) * a.F : a.dH + r * a.F;
+    float* out = lng ? a.part + (int64_t)(2 * (b / kPgChunk) + 1) * a.F : a.dH + i * a.F;
     if (lane < QP) pg_store(out, acc, lane);
   }
 }
@@ -127,13 +156,17 @@ __global__ void __launch_bounds__(kPgThreads) pg_chunks_kernel(PgArgs<T, G> a, i
 }
 
 // long rows: the chunk partials added in chunk order (one wave per row, a float4 per lane)
+template <typename R>
 static __global__ void __launch_bounds__(kPgThreads) pg_finish_kernel(
     int64_t P, int64_t n, int F, const int32_t* __restrict__ rowptr,
-    const float* __restrict__ part, float* __restrict__ dH) {
+    const float* __restrict__ part, float* __restrict__ dH, R rows) {
   const int lane = lane_id();
   const int64_t wave = ((int64_t)blockIdx.x * kPgThreads + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * kPgThreads) >> 6;
-  for (int64_t r = wave; r < n; r += nwaves) {
+  const int64_t cnt = rows.count(n);
+  for (int64_t i = wave; i < cnt; i += nwaves) {
+    const int64_t r = rows.row(i, cnt);
+    if ((uint64_t)r >= (uint64_t)n) continue;
     const int b = rowptr[r], e = rowptr[r + 1];
     if (b < 0 || (int64_t)e > 2 * P || e - b <= kPgChunk) continue;
     for (int f = 4 * lane; f < F; f += 4 * kWave) {
@@ -143,7 +176,7 @@ static __global__ void __launch_bounds__(kPgThreads) pg_finish_kernel(
         const float4 v = *reinterpret_cast<const float4*>(part + 2 * (qp / kPgChunk) * F + f);
         s = make_float4(s.x + v.x, s.y + v.y, s.z + v.z, s.w + v.w);
       }
-      *reinterpret_cast<float4*>(dH + r * F + f) = s;
+      *reinterpret_cast<float4*>(dH + i * F + f) = s;
     }
   }
 }
@@ -295,18 +328,23 @@ static void pgv_launch(const PgVecArgs<T>& a, int64_t nwin, hipStream_t s) {
                      dim3(kPgThreads), 0, s, a);
   hipLaunchKernelGGL((pgv_chunks_kernel<T>), dim3(grid_for(nwin, kPgWaves, 1 << 20)),
                      dim3(kPgThreads), 0, s, a, nwin);
-  hipLaunchKernelGGL(pg_finish_kernel, dim3(grid_for(a.n, kPgWaves, 1 << 16)), dim3(kPgThreads),
-                     0, s, a.P, a.n, a.F, a.rowptr, a.part, a.dH);
+  hipLaunchKernelGGL((pg_finish_kernel<PgAllRows>), dim3(grid_for(a.n, kPgWaves, 1 << 16)),
+                     dim3(kPgThreads), 0, s, a.P, a.n, a.F, a.rowptr, a.part, a.dH, PgAllRows{});
 }
 
-template <typename T, typename G>
-static void pg_launch(const PgArgs<T, G>& a, int64_t nwin, hipStream_t s) {
-  hipLaunchKernelGGL((pg_rows_kernel<T, G>), dim3(grid_for(a.n, kPgWaves, 1 << 20)),
-                     dim3(kPgThreads), 0, s, a);
+// a.dH: (n, F) with PgAllRows, the (cap, F) vals of the list with PgListRows
+template <typename T, typename G, typename R = PgAllRows>
+static void pg_launch(const PgArgs<T, G>& a, int64_t nwin, hipStream_t s, R rows = R{}) {
+  const int64_t ext = rows.grid_rows(a.n);
+  hipLaunchKernelGGL((pg_rows_kernel<T, G, R>), dim3(grid_for(ext, kPgWaves, 1 << 20)),
+                     dim3(kPgThreads), 0, s, a, rows);
   hipLaunchKernelGGL((pg_chunks_kernel<T, G>), dim3(grid_for(nwin, kPgWaves, 1 << 20)),
                      dim3(kPgThreads), 0, s, a, nwin);
-  hipLaunchKernelGGL(pg_finish_kernel, dim3(grid_for(a.n, kPgWaves, 1 << 16)), dim3(kPgThreads),
-                     0, s, a.P, a.n, a.F, a.rowptr, a.part, a.dH);
+  hipLaunchKernelGGL((pg_finish_kernel<R>), dim3(grid_for(ext, kPgWaves, 1 << 16)),
+                     dim3(kPgThreads), 0, s, a.P, a.n, a.F, a.rowptr, a.part, a.dH, rows);
 }
+
+// the list's capacity (msha_plan_rows): no plan names more rows than it has endpoints
+static inline int64_t pg_rows_cap(int64_t n, int64_t P) { return n < 2 * P ? n : 2 * P; }
 
 }  // namespace msha

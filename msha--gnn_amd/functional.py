@@ -1623,6 +1623,73 @@ def pair_plan(src, dst, n: int) -> PairPlan:
     return PairPlan(n, P, rowptr, ent, tab)
 
 
+def plan_rows(plan: PairPlan):
+    """The touched-row list of ``plan`` (``msha_plan_rows``): ``(rows, n_rows)`` with ``rows``
+    int32 of capacity ``min(n, 2P)``, the ascending ids of the table rows that have an
+    endpoint, -1 past the count, and ``n_rows`` a device int32 scalar.  Padding pairs touch
+    no row.  A pure function of the plan: integer work, nothing read back (capturable); it is
+    kept on the plan and lives as long as the plan does."""
+    if not isinstance(plan, PairPlan) or plan.rowptr is None:
+        raise ValueError("plan_rows: plan must be a PairPlan (pair_plan / context_plan)")
+    got = getattr(plan, "_rows", None)
+    if got is not None:
+        return got
+    _lib.require_cuda(plan.rowptr)
+    n, P, dev = plan.n, plan.n_pairs, plan.rowptr.device
+    rows = torch.empty(min(n, 2 * P), dtype=torch.int32, device=dev)
+    n_rows = torch.empty((), dtype=torch.int32, device=dev)
+    ws = _workspace(dev, _lib.fn("msha_plan_rows_workspace_size")(n))
+    _lib.call("msha_plan_rows", n, P, plan.rowptr.data_ptr(),
+              rows.data_ptr() if rows.numel() else None, n_rows.data_ptr(), ws.data_ptr(),
+              ws.numel(), _stream(plan.rowptr))
+    plan._rows = (rows, n_rows)
+    return plan._rows
+
+
+class RowGrad:
+    """The gradient of an (n, F) table on the rows a batch touches: ``values[i]`` (fp32) is
+    the gradient of row ``rows[i]`` for ``i < n_rows`` (``plan_rows``: ``rows`` ascending,
+    -1 past the count, ``n_rows`` a device scalar) and zero past it; every other row's
+    gradient is zero.  ``shape`` is the table's.  ``optim.Adam`` steps a table registered
+    with ``fuse_row_grad`` from it."""
+
+    def __init__(self, rows, n_rows, values, shape):
+        self.rows, self.n_rows, self.values, self.shape = rows, n_rows, values, tuple(shape)
+
+    def to_dense(self):
+        """The (n, F) fp32 gradient (debugging): a scatter into zeros, nothing read back."""
+        n, Fd = self.shape
+        out = torch.zeros(n + 1, Fd, dtype=self.values.dtype, device=self.values.device)
+        idx = self.rows.to(torch.int64)
+        out[torch.where(idx >= 0, idx, torch.full_like(idx, n))] = self.values  # -1: row n
+        return out[:n]
+
+
+def _row_leaf(h, plan):
+    """``h`` itself when it is a leaf table registered with ``optim.Adam.fuse_row_grad`` that
+    needs a gradient (its backward then forms a ``RowGrad``), else None."""
+    if plan is None or not (h.requires_grad and h.is_leaf and h.is_contiguous()):
+        return None
+    from .optim import row_optimizer_of
+
+    return h if row_optimizer_of(h) is not None else None
+
+
+def _stash_rows(leaf, plan, launch):
+    """Backward of a registered leaf: ``launch(rows, n_rows, cap, vals)`` fills the compact
+    gradient, which goes to the leaf's optimizer in place of ``.grad``."""
+    from .optim import row_optimizer_of
+
+    opt = row_optimizer_of(leaf)
+    if opt is None:
+        raise RuntimeError("msha: the optimizer of a fuse_row_grad table is gone before its "
+                           "backward")
+    rows, n_rows = plan_rows(plan)
+    vals = torch.empty(rows.numel(), leaf.shape[1], dtype=torch.float32, device=leaf.device)
+    opt.stash_row_grad(leaf, RowGrad(rows, n_rows, vals, leaf.shape))  # raises on a second one
+    launch(rows.data_ptr(), n_rows.data_ptr(), rows.numel(), vals.data_ptr())
+
+
 def sample_negatives(graph, src, k: int = 1, n_cand: int | None = None, seed: int | None = None,
                      offset: int = 0, col_offset: int = 0):
     """``k`` non-edges per positive: ``(src_rep, dst_neg)``, int64 of length P * k, the pair
@@ -1690,6 +1757,7 @@ class _LinkBCE(torch.autograd.Function):
                   src.data_ptr(), dst.data_ptr(), target.data_ptr(), _lib.ptr(weight),
                   z.data_ptr(), loss.data_ptr(), npad.data_ptr(), ws.data_ptr(), ws.numel(), s)
         ctx.plan, ctx.dt = plan, dt
+        ctx.leaf = _row_leaf(h, plan)  # the registered table itself (its optimizer updates it)
         ctx.save_for_backward(hh, src, dst, target, weight, z)
         ctx.mark_non_differentiable(z, npad)
         return loss, z, npad
@@ -1701,13 +1769,19 @@ class _LinkBCE(torch.autograd.Function):
         P, dev = src.numel(), hh.device
         plan = ctx.plan
         g = gloss.detach().to(torch.float32).reshape(1).contiguous()
-        dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
         ws = _workspace(dev, _lib.fn("msha_link_bce_bwd_workspace_size")(P, Fd))
-        _lib.call("msha_link_bce_bwd", P, Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n,
-                  src.data_ptr(), dst.data_ptr(), target.data_ptr(), _lib.ptr(weight),
-                  z.data_ptr(), g.data_ptr(), plan.rowptr.data_ptr(), plan.ent.data_ptr(),
-                  plan.chunk_tab.data_ptr(), dH.data_ptr(), ws.data_ptr(), ws.numel(),
-                  _stream(hh))
+        args = (P, Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n, src.data_ptr(),
+                dst.data_ptr(), target.data_ptr(), _lib.ptr(weight), z.data_ptr(), g.data_ptr(),
+                plan.rowptr.data_ptr(), plan.ent.data_ptr(), plan.chunk_tab.data_ptr())
+        tail = (ws.data_ptr(), ws.numel(), _stream(hh))
+        if ctx.leaf is not None and ctx.needs_input_grad[0]:
+            # a fuse_row_grad table: the touched rows' gradient goes to its optimizer, no
+            # (n, F) buffer is formed and .grad stays None
+            _stash_rows(ctx.leaf, plan, lambda *rows_vals: _lib.call(
+                "msha_link_bce_bwd_rows", *args, *rows_vals, *tail))
+            return None, None, None, None, None, None
+        dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
+        _lib.call("msha_link_bce_bwd", *args, dH.data_ptr(), *tail)
         return (dH if ctx.dt == torch.float32 else dH.to(ctx.dt)), None, None, None, None, None
 
 
@@ -2018,6 +2092,7 @@ class _LinkDistill(torch.autograd.Function):
                   w_rank, w_dist, w_prob, logits.data_ptr(), g.data_ptr(), loss.data_ptr(),
                   terms.data_ptr(), npad.data_ptr(), ws.data_ptr(), ws.numel(), s)
         ctx.plan, ctx.dt = plan, dt
+        ctx.leaf = _row_leaf(h, plan)  # the registered table itself (its optimizer updates it)
         ctx.save_for_backward(hh, context, g)
         ctx.mark_non_differentiable(terms, logits, npad)
         return loss, terms, logits, npad
@@ -2029,12 +2104,17 @@ class _LinkDistill(torch.autograd.Function):
         P, dev = context.numel(), hh.device
         plan = ctx.plan
         gl = gloss.detach().to(torch.float32).reshape(1).contiguous()
-        dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
         ws = _workspace(dev, _lib.fn("msha_pair_grad_bwd_workspace_size")(P, Fd))
-        _lib.call("msha_pair_grad_bwd", P, Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n,
-                  plan.src.data_ptr(), context.data_ptr(), g.data_ptr(), gl.data_ptr(),
-                  plan.rowptr.data_ptr(), plan.ent.data_ptr(), plan.chunk_tab.data_ptr(),
-                  dH.data_ptr(), ws.data_ptr(), ws.numel(), _stream(hh))
+        args = (P, Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n, plan.src.data_ptr(),
+                context.data_ptr(), g.data_ptr(), gl.data_ptr(), plan.rowptr.data_ptr(),
+                plan.ent.data_ptr(), plan.chunk_tab.data_ptr())
+        tail = (ws.data_ptr(), ws.numel(), _stream(hh))
+        if ctx.leaf is not None and ctx.needs_input_grad[0]:  # a fuse_row_grad table
+            _stash_rows(ctx.leaf, plan, lambda *rows_vals: _lib.call(
+                "msha_pair_grad_bwd_rows", *args, *rows_vals, *tail))
+            return (None,) * 11
+        dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
+        _lib.call("msha_pair_grad_bwd", *args, dH.data_ptr(), *tail)
         return ((dH if ctx.dt == torch.float32 else dH.to(ctx.dt)),) + (None,) * 10
 
 

@@ -418,7 +418,9 @@ class LinkPredictor(torch.nn.Module):
         the caller's gather fused and a deterministic gradient to ``h``
         (``functional.link_bce_loss``: the sum over pairs under ``weight``, the mean
         without).  'inner' only: the reference's 'mlp' head returns a (B, hidden) vector per
-        pair (LLP.py:107-111), which gives no scalar logit to take the loss of."""
+        pair (LLP.py:107-111), which gives no scalar logit to take the loss of.  When ``h``
+        is itself a table registered with ``optim.Adam.fuse_row_grad``, only the rows the
+        pairs touch get a gradient and an update (the registration is on the table)."""
         if self.predictor != "inner":
             raise ValueError(f"LinkPredictor.loss needs the 'inner' predictor: "
                              f"{self.predictor!r} scores a pair with a vector (LLP.py:107-115), "
@@ -432,7 +434,8 @@ class LinkPredictor(torch.nn.Module):
         deterministic gradient to ``h``).  The teacher is its logits ``(A, K)`` or its node
         table ``teacher_h``, scored by the same inner product.  'inner' only: the
         reference's 'mlp' head returns a (B, hidden) vector per pair (LLP.py:107-111), which
-        gives no scalar logit to distil."""
+        gives no scalar logit to distil.  A table registered with
+        ``optim.Adam.fuse_row_grad`` is updated on its touched rows only, as in ``loss``."""
         if self.predictor != "inner":
             raise ValueError(f"LinkPredictor.distill_loss needs the 'inner' predictor: "
                              f"{self.predictor!r} scores a pair with a vector (LLP.py:107-115), "

@@ -16,6 +16,12 @@ gradient is never written or re-read, and every parameter still updates in ONE l
 at ``step()``.  The parameter's ``.grad`` stays None.  (One backward per step for a fused
 parameter: a second backward before ``step()`` raises, as accumulation would need the
 gradient this path never forms.)
+
+``fuse_row_grad(param)``: an embedding-style table trained by ``functional.link_bce_loss`` /
+``link_distill_loss``.  Their backward hands this optimizer the gradient of the rows the
+batch touches (``functional.RowGrad``) instead of an (n, F) ``.grad``, and ``step()`` runs
+``msha_adam_rows_step`` over those rows: the same update with one global step count, the
+other rows neither read nor written.  ``state_dict`` is unchanged.
 """
 from __future__ import annotations
 
@@ -131,6 +137,18 @@ class Adam(torch.optim.Optimizer):
         for group in self.param_groups:
             by_dev = {}
             for p in group["params"]:
+                if row_optimizer_of(p) is self:
+                    self._check_row_group(group)
+                    rg = getattr(p, "_msha_row_grad", None)
+                    if rg is not None:  # the touched rows' gradient: a lazy step over them
+                        if p.grad is not None:
+                            raise RuntimeError(
+                                "msha Adam: a fuse_row_grad parameter has both a row gradient "
+                                "and a .grad (it has another consumer besides its link loss): "
+                                "do not register it")
+                        p._msha_row_grad = None
+                        self._rows_step(group, p, rg)
+                        continue
                 stash = getattr(p, "_msha_dropout_grad", None)
                 if stash is not None:  # fused: the dropout's output gradient + its mask
                     if p.grad is not None:
@@ -161,6 +179,68 @@ class Adam(torch.optim.Optimizer):
             for p in group["params"]:
                 if getattr(p, "_msha_dropout_grad", None) is not None:
                     p._msha_dropout_grad = None
+                if getattr(p, "_msha_row_grad", None) is not None:
+                    p._msha_row_grad = None
+
+    # ------------------------------------------------- row-sparse table updates
+    @staticmethod
+    def _check_row_group(group):
+        if group["weight_decay"] != 0:
+            raise ValueError("msha Adam: a fuse_row_grad table needs weight_decay == 0 in its "
+                             "parameter group (L2 decay makes the gradient dense; this "
+                             "optimizer has no decoupled decay)")
+
+    def fuse_row_grad(self, param):
+        """Train the 2-D leaf table ``param`` at the cost of the rows a batch touches;
+        returns ``param``.  ``functional.link_bce_loss`` / ``link_distill_loss`` called on
+        the table itself then hand their backward's ``functional.RowGrad`` (the touched rows
+        of the plan and their fp32 gradient rows, bit for bit the dense gradient's) to this
+        optimizer in place of ``param.grad``, which stays None: no (n, F) gradient is
+        allocated.  ``step()`` runs ``msha_adam_rows_step`` over those rows: this
+        optimizer's update with one global step count, for the touched rows only; the
+        moments of the other rows are not decayed (``torch.optim.SparseAdam``'s rule with
+        eps inside the bias correction).  A step that touches every row leaves the bits of
+        the unregistered update.  One row gradient per step (a second backward before
+        ``step()`` raises); the group's ``weight_decay`` must be 0.  A view, a cast or an
+        encoder's output of the table takes the dense path as before.  When a batch names
+        every row (P in the millions on a 100k-row table) the list adds work and nothing is
+        saved: the registered step may then be slower than the dense one
+        (profiles/row_adam_ab)."""
+        group = self._group_of(param)  # must be ours
+        if param.dim() != 2 or not param.is_leaf:
+            raise ValueError("msha Adam: fuse_row_grad takes a 2-D leaf table, got "
+                             f"{tuple(param.shape)}")
+        self._check_row_group(group)
+        param._msha_row_adam = weakref.ref(self)
+        return param
+
+    def stash_row_grad(self, param, row_grad):
+        """Called from a link loss's backward: keep the table's ``functional.RowGrad`` for
+        ``step()`` in place of ``param.grad``."""
+        if getattr(param, "_msha_row_grad", None) is not None:
+            raise RuntimeError("msha Adam: a fuse_row_grad table got a second backward before "
+                               "step(); one row gradient per step (do not register a table "
+                               "that two losses share)")
+        if tuple(row_grad.shape) != tuple(param.shape):
+            raise ValueError("msha Adam: the row gradient is not of this table's shape")
+        param._msha_row_grad = row_grad
+
+    def row_grad_of(self, param):
+        """The pending ``functional.RowGrad`` of a registered table, or None."""
+        return getattr(param, "_msha_row_grad", None)
+
+    def _rows_step(self, group, p, rg):
+        _lib.require_cuda(p, rg.values)
+        if p.dtype not in _DT or not p.is_contiguous():
+            raise TypeError("msha Adam: a fuse_row_grad table is a contiguous fp32 / bf16 "
+                            f"parameter (got {p.dtype})")
+        st = self._state_of(p)
+        b1, b2 = group["betas"]
+        _lib.call("msha_adam_rows_step", p.shape[0], p.shape[1], _DT[p.dtype], p.data_ptr(),
+                  st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr(),
+                  rg.rows.data_ptr(), rg.n_rows.data_ptr(), rg.rows.numel(),
+                  rg.values.data_ptr(), float(group["lr"]), float(b1), float(b2),
+                  float(group["eps"]), _lib.stream_handle(p.device))
 
     # ---------------------------------------------- fused dropout-backward updates
     def fuse_dropout_grad(self, param):
@@ -179,6 +259,12 @@ class Adam(torch.optim.Optimizer):
         dout = dout.contiguous()
         self._check(param, dout)
         param._msha_dropout_grad = (dout, float(p), int(seed))
+
+
+def row_optimizer_of(param):
+    """The msha Adam registered by ``fuse_row_grad`` for ``param`` (or None)."""
+    ref = getattr(param, "_msha_row_adam", None)
+    return ref() if ref is not None else None
 
 
 def fused_optimizer_of(param):
