@@ -344,6 +344,7 @@ __global__ void __launch_bounds__(kDsFinThreads) ds_final_kernel(
 // the per-pair factor, loaded
 struct DsLoadG {
   const float* g;
+  bool ok() const { return g != nullptr; }
   __device__ __forceinline__ float at(int64_t p, float gl) const { return gl * g[p]; }
 };
 
@@ -443,38 +444,7 @@ extern "C" int msha_link_distill_fwd(int64_t n_anchors, int32_t k, int32_t feat,
 
 extern "C" size_t msha_pair_grad_bwd_workspace_size(int64_t n_pairs, int32_t feat) {
   if (n_pairs < 0 || n_pairs > kPgMaxPairs || feat < 1) return 0;
-  return pg_align((size_t)2 * pg_windows(n_pairs) * feat * 4);
-}
-
-// the dense gradient (R = PgAllRows, out = dH) and the touched-row one (R = PgListRows, out =
-// vals): one argument check, one launch sequence
-template <typename R>
-static int pgb_bwd(const char* name, int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
-                   int64_t ld, int64_t n, const int64_t* src, const int64_t* dst, const float* g,
-                   const float* gloss, const int32_t* plan_rowptr, const int32_t* plan_ent,
-                   const int32_t* plan_chunk_tab, float* out, void* ws, size_t ws_bytes,
-                   msha_stream_t stream, R rows) {
-  const std::string nm(name);
-  MSHA_ARG_CHECK(src && dst && g && gloss && plan_rowptr && plan_ent && plan_chunk_tab && out,
-                 nm + ": null pointer");
-  MSHA_ARG_CHECK(((uintptr_t)out % 16) == 0,
-                 nm + ": " + R::kOut + " must be 16-byte aligned");
-  const int64_t nwin = pg_windows(n_pairs);
-  MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= pg_align((size_t)2 * nwin * feat * 4) &&
-                     ((uintptr_t)ws % 16) == 0,
-                 nm + ": workspace too small or unaligned (msha_pair_grad_bwd_workspace_size)");
-  hipStream_t s = (hipStream_t)stream;
-  const DsLoadG lg = {g};
-  if (dtype == MSHA_DTYPE_BF16) {
-    const PgArgs<bf16_t, DsLoadG> a = {n_pairs, n, ld, (int)feat, (const bf16_t*)h, src, dst, lg,
-                                       gloss, plan_rowptr, plan_ent, plan_chunk_tab, (float*)ws, out};
-    pg_launch(a, nwin, s, rows);
-  } else {
-    const PgArgs<float, DsLoadG> a = {n_pairs, n, ld, (int)feat, (const float*)h, src, dst, lg,
-                                      gloss, plan_rowptr, plan_ent, plan_chunk_tab, (float*)ws, out};
-    pg_launch(a, nwin, s, rows);
-  }
-  return check_launch(name);
+  return pg_workspace_bytes(n_pairs, feat);
 }
 
 extern "C" int msha_pair_grad_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
@@ -484,8 +454,9 @@ extern "C" int msha_pair_grad_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, 
                                   void* ws, size_t ws_bytes, msha_stream_t stream) {
   const int rc = pg_table_check("pair_grad_bwd", n_pairs, feat, dtype, h, ld, n);
   if (rc != MSHA_OK) return rc;
-  return pgb_bwd("pair_grad_bwd", n_pairs, feat, dtype, h, ld, n, src, dst, g, gloss, plan_rowptr,
-                 plan_ent, plan_chunk_tab, dH, ws, ws_bytes, stream, PgAllRows{});
+  return pg_run("pair_grad_bwd", "msha_pair_grad_bwd_workspace_size", n_pairs, feat, dtype, h, ld,
+                n, src, dst, plan_rowptr, plan_ent, plan_chunk_tab, DsLoadG{g}, gloss, dH, ws,
+                ws_bytes, stream, PgAllRows{});
 }
 
 extern "C" int msha_pair_grad_bwd_rows(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
@@ -500,7 +471,7 @@ extern "C" int msha_pair_grad_bwd_rows(int64_t n_pairs, int32_t feat, int32_t dt
   MSHA_ARG_CHECK(rows && n_rows, "pair_grad_bwd_rows: null pointer");
   MSHA_ARG_CHECK(cap == pg_rows_cap(n, n_pairs),
                  "pair_grad_bwd_rows: cap must be min(n, 2 * n_pairs) (msha_plan_rows)");
-  return pgb_bwd("pair_grad_bwd_rows", n_pairs, feat, dtype, h, ld, n, src, dst, g, gloss,
-                 plan_rowptr, plan_ent, plan_chunk_tab, vals, ws, ws_bytes, stream,
-                 PgListRows{rows, n_rows, cap});
+  return pg_run("pair_grad_bwd_rows", "msha_pair_grad_bwd_workspace_size", n_pairs, feat, dtype,
+                h, ld, n, src, dst, plan_rowptr, plan_ent, plan_chunk_tab, DsLoadG{g}, gloss, vals,
+                ws, ws_bytes, stream, PgListRows{rows, n_rows, cap});
 }

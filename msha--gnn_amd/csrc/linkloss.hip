@@ -398,12 +398,11 @@ __device__ __forceinline__ float lb_grad(float z, float y, float w, float gl) {
 struct LbBceG {
   const float *z, *y, *w;
   float winv;
+  bool ok() const { return z != nullptr && y != nullptr; }
   __device__ __forceinline__ float at(int64_t p, float gl) const {
     return lb_grad(z[p], y[p], w != nullptr ? w[p] : winv, gl);
   }
 };
-
-static size_t ll_align(size_t x) { return pg_align(x); }
 
 struct PlLayout {
   int64_t nb;
@@ -417,25 +416,21 @@ static PlLayout pl_layout(int64_t P) {
   size_t off = 0;
   for (int i = 0; i < 2; ++i) {
     L.keys[i] = off;
-    off += ll_align((size_t)E * 4);
+    off += pg_align((size_t)E * 4);
   }
   for (int i = 0; i < 2; ++i) {
     L.pay[i] = off;
-    off += ll_align((size_t)E * 4);
+    off += pg_align((size_t)E * 4);
   }
   L.hist = off;
-  off += ll_align((size_t)256 * L.nb * 4);
+  off += pg_align((size_t)256 * L.nb * 4);
   L.tot = off;
-  off += ll_align((size_t)256 * 4);
+  off += pg_align((size_t)256 * 4);
   L.total = off;
   return L;
 }
 
-static int64_t pl_windows(int64_t P) { return pg_windows(P); }
 static int64_t fwd_blocks(int64_t P) { return P > 0 ? (P + kFwdTile - 1) / kFwdTile : 1; }
-constexpr int64_t kMaxPairs = kPgMaxPairs;  // 2P < 2^31
-
-static bool lb_width_ok(int32_t feat, int32_t dtype) { return pg_width_ok(feat, dtype); }
 
 }  // namespace msha
 
@@ -466,12 +461,12 @@ extern "C" int msha_negative_sample(int64_t n_pos, int32_t k, const int64_t* src
 extern "C" int32_t msha_pair_plan_chunk(void) { return kPlChunk; }
 
 extern "C" int64_t msha_pair_plan_chunk_slots(int64_t n_pairs) {
-  if (n_pairs < 0 || n_pairs > kMaxPairs) return 0;
-  return pl_windows(n_pairs);
+  if (n_pairs < 0 || n_pairs > kPgMaxPairs) return 0;
+  return pg_windows(n_pairs);
 }
 
 extern "C" size_t msha_pair_plan_workspace_size(int64_t n_pairs) {
-  if (n_pairs < 0 || n_pairs > kMaxPairs) return 0;
+  if (n_pairs < 0 || n_pairs > kPgMaxPairs) return 0;
   return pl_layout(n_pairs).total;
 }
 
@@ -479,7 +474,7 @@ extern "C" int msha_pair_plan(int64_t n_pairs, int64_t n, const int64_t* src, co
                               int32_t* rowptr, int32_t* ent, int32_t* chunk_tab, void* ws,
                               size_t ws_bytes, msha_stream_t stream) {
   MSHA_ARG_CHECK(n_pairs >= 0 && n >= 1, "pair_plan: bad sizes (n_pairs >= 0, n >= 1)");
-  MSHA_ARG_CHECK(n_pairs <= kMaxPairs, "pair_plan: 2 * n_pairs must be below 2^31");
+  MSHA_ARG_CHECK(n_pairs <= kPgMaxPairs, "pair_plan: 2 * n_pairs must be below 2^31");
   MSHA_ARG_CHECK(n < ((int64_t)1 << 31) - 1, "pair_plan: n must be below 2^31 - 1");
   MSHA_ARG_CHECK(rowptr && chunk_tab && (n_pairs == 0 || (src && dst && ent)),
                  "pair_plan: null pointer");
@@ -511,29 +506,24 @@ extern "C" int msha_pair_plan(int64_t n_pairs, int64_t n, const int64_t* src, co
   }
   hipLaunchKernelGGL(pl_rows_kernel, dim3(grid_for(E > n ? E : n + 1, kLlThreads, 1 << 16)), blk, 0,
                      s, E, n, keys[cur], pay[cur], rowptr, ent);
-  const int64_t nwin = pl_windows(n_pairs);
+  const int64_t nwin = pg_windows(n_pairs);
   hipLaunchKernelGGL(pl_chunks_kernel, dim3(grid_for(nwin, kLlThreads, 1 << 16)), blk, 0, s, nwin,
                      n, rowptr, chunk_tab);
   return check_launch("pair_plan");
 }
 
 extern "C" int msha_link_bce_supported(int32_t feat, int32_t dtype) {
-  return lb_width_ok(feat, dtype) ? 1 : 0;
+  return pg_width_ok(feat, dtype) ? 1 : 0;
 }
 
 extern "C" size_t msha_link_bce_fwd_workspace_size(int64_t n_pairs) {
-  if (n_pairs < 0 || n_pairs > kMaxPairs) return 0;
-  return 2 * ll_align((size_t)fwd_blocks(n_pairs) * 4);
+  if (n_pairs < 0 || n_pairs > kPgMaxPairs) return 0;
+  return 2 * pg_align((size_t)fwd_blocks(n_pairs) * 4);
 }
 
 extern "C" size_t msha_link_bce_bwd_workspace_size(int64_t n_pairs, int32_t feat) {
-  if (n_pairs < 0 || n_pairs > kMaxPairs || feat < 1) return 0;
-  return ll_align((size_t)2 * pl_windows(n_pairs) * feat * 4);
-}
-
-static int lb_table_check(const char* name, int64_t n_pairs, int32_t feat, int32_t dtype,
-                          const void* h, int64_t ld, int64_t n) {
-  return pg_table_check(name, n_pairs, feat, dtype, h, ld, n);
+  if (n_pairs < 0 || n_pairs > kPgMaxPairs || feat < 1) return 0;
+  return pg_workspace_bytes(n_pairs, feat);
 }
 
 extern "C" int msha_link_bce_fwd(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
@@ -541,11 +531,11 @@ extern "C" int msha_link_bce_fwd(int64_t n_pairs, int32_t feat, int32_t dtype, c
                                  const float* target, const float* weight, float* z, float* loss,
                                  int32_t* n_pad, void* ws, size_t ws_bytes,
                                  msha_stream_t stream) {
-  const int rc = lb_table_check("link_bce_fwd", n_pairs, feat, dtype, h, ld, n);
+  const int rc = pg_table_check("link_bce_fwd", n_pairs, feat, dtype, h, ld, n);
   if (rc != MSHA_OK) return rc;
   MSHA_ARG_CHECK(src && dst && target && z && loss && n_pad, "link_bce_fwd: null pointer");
   const int64_t nb = fwd_blocks(n_pairs);
-  const size_t half = ll_align((size_t)nb * 4);
+  const size_t half = pg_align((size_t)nb * 4);
   MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= 2 * half && ((uintptr_t)ws % 16) == 0,
                  "link_bce_fwd: workspace too small or unaligned "
                  "(msha_link_bce_fwd_workspace_size)");
@@ -566,38 +556,9 @@ extern "C" int msha_link_bce_fwd(int64_t n_pairs, int32_t feat, int32_t dtype, c
   return check_launch("link_bce_fwd");
 }
 
-// the dense gradient (R = PgAllRows, out = dH) and the touched-row one (R = PgListRows, out =
-// vals): one argument check, one launch sequence
-template <typename R>
-static int lb_bwd(const char* name, int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
-                  int64_t ld, int64_t n, const int64_t* src, const int64_t* dst,
-                  const float* target, const float* weight, const float* z, const float* gloss,
-                  const int32_t* plan_rowptr, const int32_t* plan_ent,
-                  const int32_t* plan_chunk_tab, float* out, void* ws, size_t ws_bytes,
-                  msha_stream_t stream, R rows) {
-  const std::string nm(name);
-  MSHA_ARG_CHECK(src && dst && target && z && gloss && plan_rowptr && plan_ent &&
-                     plan_chunk_tab && out,
-                 nm + ": null pointer");
-  MSHA_ARG_CHECK(((uintptr_t)out % 16) == 0,
-                 nm + ": " + R::kOut + " must be 16-byte aligned");
-  const int64_t nwin = pl_windows(n_pairs);
-  MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= ll_align((size_t)2 * nwin * feat * 4) &&
-                     ((uintptr_t)ws % 16) == 0,
-                 nm + ": workspace too small or unaligned (msha_link_bce_bwd_workspace_size)");
-  hipStream_t s = (hipStream_t)stream;
-  const float winv = (float)(1.0 / (double)n_pairs);
-  const LbBceG g = {z, target, weight, winv};
-  if (dtype == MSHA_DTYPE_BF16) {
-    const PgArgs<bf16_t, LbBceG> a = {n_pairs, n, ld, (int)feat, (const bf16_t*)h, src, dst, g,
-                                      gloss, plan_rowptr, plan_ent, plan_chunk_tab, (float*)ws, out};
-    pg_launch(a, nwin, s, rows);
-  } else {
-    const PgArgs<float, LbBceG> a = {n_pairs, n, ld, (int)feat, (const float*)h, src, dst, g,
-                                     gloss, plan_rowptr, plan_ent, plan_chunk_tab, (float*)ws, out};
-    pg_launch(a, nwin, s, rows);
-  }
-  return check_launch(name);
+static LbBceG lb_factor(int64_t n_pairs, const float* z, const float* target,
+                        const float* weight) {
+  return {z, target, weight, (float)(1.0 / (double)n_pairs)};
 }
 
 extern "C" int msha_link_bce_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, const void* h,
@@ -606,10 +567,11 @@ extern "C" int msha_link_bce_bwd(int64_t n_pairs, int32_t feat, int32_t dtype, c
                                  const float* gloss, const int32_t* plan_rowptr,
                                  const int32_t* plan_ent, const int32_t* plan_chunk_tab, float* dH,
                                  void* ws, size_t ws_bytes, msha_stream_t stream) {
-  const int rc = lb_table_check("link_bce_bwd", n_pairs, feat, dtype, h, ld, n);
+  const int rc = pg_table_check("link_bce_bwd", n_pairs, feat, dtype, h, ld, n);
   if (rc != MSHA_OK) return rc;
-  return lb_bwd("link_bce_bwd", n_pairs, feat, dtype, h, ld, n, src, dst, target, weight, z,
-                gloss, plan_rowptr, plan_ent, plan_chunk_tab, dH, ws, ws_bytes, stream,
+  return pg_run("link_bce_bwd", "msha_link_bce_bwd_workspace_size", n_pairs, feat, dtype, h, ld,
+                n, src, dst, plan_rowptr, plan_ent, plan_chunk_tab,
+                lb_factor(n_pairs, z, target, weight), gloss, dH, ws, ws_bytes, stream,
                 PgAllRows{});
 }
 
@@ -621,12 +583,13 @@ extern "C" int msha_link_bce_bwd_rows(int64_t n_pairs, int32_t feat, int32_t dty
                                       const int32_t* plan_chunk_tab, const int32_t* rows,
                                       const int32_t* n_rows, int64_t cap, float* vals, void* ws,
                                       size_t ws_bytes, msha_stream_t stream) {
-  const int rc = lb_table_check("link_bce_bwd_rows", n_pairs, feat, dtype, h, ld, n);
+  const int rc = pg_table_check("link_bce_bwd_rows", n_pairs, feat, dtype, h, ld, n);
   if (rc != MSHA_OK) return rc;
   MSHA_ARG_CHECK(rows && n_rows, "link_bce_bwd_rows: null pointer");
   MSHA_ARG_CHECK(cap == pg_rows_cap(n, n_pairs),
                  "link_bce_bwd_rows: cap must be min(n, 2 * n_pairs) (msha_plan_rows)");
-  return lb_bwd("link_bce_bwd_rows", n_pairs, feat, dtype, h, ld, n, src, dst, target, weight, z,
-                gloss, plan_rowptr, plan_ent, plan_chunk_tab, vals, ws, ws_bytes, stream,
+  return pg_run("link_bce_bwd_rows", "msha_link_bce_bwd_workspace_size", n_pairs, feat, dtype, h,
+                ld, n, src, dst, plan_rowptr, plan_ent, plan_chunk_tab,
+                lb_factor(n_pairs, z, target, weight), gloss, vals, ws, ws_bytes, stream,
                 PgListRows{rows, n_rows, cap});
 }

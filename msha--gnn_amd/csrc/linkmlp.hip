@@ -424,7 +424,7 @@ static LmBwdLayout lm_bwd_layout(int64_t P, int32_t feat, int32_t hidden) {
   L.wpart = off;
   off += pg_align((size_t)lm_wg_blocks(P) * ((size_t)hidden * feat + hidden) * 4);
   L.pgpart = off;
-  off += pg_align((size_t)2 * pg_windows(P) * feat * 4);
+  off += pg_workspace_bytes(P, feat);
   L.total = off;
   return L;
 }
@@ -574,17 +574,10 @@ extern "C" int msha_link_mlp_bwd(int64_t n_pairs, int32_t feat, int32_t hidden, 
     const int grc = msha_gemm_f32(n_pairs, F, N, dz, N, 1, W32, F, 1, dx, F, 0.f, 1, nullptr, 0,
                                   stream);
     if (grc != MSHA_OK) return grc;
-    const int64_t nwin = pg_windows(n_pairs);
-    float* pgpart = (float*)(w + L.pgpart);
-    if (dtype == MSHA_DTYPE_BF16) {
-      const PgVecArgs<bf16_t> a = {n_pairs, n, ld, F, (const bf16_t*)h, src, dst, dx,
-                                   plan_rowptr, plan_ent, plan_chunk_tab, pgpart, dH};
-      pgv_launch(a, nwin, s);
-    } else {
-      const PgVecArgs<float> a = {n_pairs, n, ld, F, (const float*)h, src, dst, dx,
-                                  plan_rowptr, plan_ent, plan_chunk_tab, pgpart, dH};
-      pgv_launch(a, nwin, s);
-    }
+    // dH from dx under the plan (pair_grad.h); dx carries gloss already (lm_dz_kernel)
+    return pg_run("link_mlp_bwd", "msha_link_mlp_bwd_workspace_size", n_pairs, feat, dtype, h, ld,
+                  n, src, dst, plan_rowptr, plan_ent, plan_chunk_tab, PgDx{dx}, nullptr, dH,
+                  w + L.pgpart, L.total - L.pgpart, stream, PgAllRows{});
   }
   return check_launch("link_mlp_bwd");
 }

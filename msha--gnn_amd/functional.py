@@ -1739,14 +1739,85 @@ def sample_negatives(graph, src, k: int = 1, n_cand: int | None = None, seed: in
     return src_rep, dst_neg
 
 
+# The front shared by the table losses (link_bce_loss, link_mlp_loss, link_distill_loss,
+# link_match_loss).  `name` is the loss's name in the message.
+def _rows16(t):
+    """``t`` itself when the kernels can read it in place (unit column stride, 16-byte row
+    pitch and base), else a contiguous copy."""
+    esz = t.element_size()
+    ok = t.stride(1) == 1 and (t.stride(0) * esz) % 16 == 0 and t.data_ptr() % 16 == 0
+    return t if ok else t.contiguous()
+
+
+def _check_table_dtype(name, t, what="table"):
+    if t.dtype not in (torch.float32, BF16):
+        raise TypeError(f"{name} takes a float32 or bfloat16 {what}, got {t.dtype}")
+
+
+def _check_table_shape(name, t, arg="h", form="(n, F)", rows=False):
+    if t.dim() != 2 or (rows and t.shape[0] < 1):
+        raise ValueError(f"{name}: {arg} must be {form}, got {tuple(t.shape)}")
+
+
+def _check_table_width(name, *tables):
+    for t in tables:
+        if t is not None and not _lib.fn("msha_link_bce_supported")(t.shape[1], _code(t.dtype)):
+            raise ValueError(f"{name}: feature width {t.shape[1]} of a {t.dtype} table is not "
+                             f"supported (a power of two, 16 bytes to 64 lanes x 16 bytes)")
+
+
+def _check_plan(name, plan, n, P, context=False):
+    """``plan`` is None or the PairPlan of a list of P pairs over n rows (``context``: one that
+    carries its flat src, a ``context_plan``)."""
+    if plan is None:
+        return
+    ok = isinstance(plan, PairPlan) and plan.n == n and plan.n_pairs == P
+    if context and not (ok and getattr(plan, "src", None) is not None):
+        raise ValueError(f"{name}: plan is not a context_plan of this context and table")
+    if not ok:
+        raise ValueError(f"{name}: plan is not a PairPlan of this pair list and table")
+
+
+def _check_same_device(name, h, *tensors):
+    for t in tensors:
+        if t is not None and t.device != h.device:
+            raise ValueError(f"{name}: every tensor must be on the table's device")
+
+
+def _table_grad(dH, dt):
+    """The fp32 sum ``dH`` as the gradient of a table of dtype ``dt``."""
+    return dH if dt == torch.float32 else dH.to(dt)
+
+
+def _pair_grad_backward(ctx, gloss, hh, dense, rows, pair_args):
+    """The backward of a loss whose table gradient is a pair-list sum under ``ctx.plan``
+    (pair_grad.h): entry point ``dense`` for an (n, F) gradient, ``rows`` for the touched rows
+    of a ``fuse_row_grad`` leaf.  ``pair_args``: the pair list's and the factor's pointers, the
+    arguments between ``n`` and ``gloss``."""
+    n, Fd = hh.shape
+    plan, dev = ctx.plan, hh.device
+    P = plan.n_pairs
+    g = gloss.detach().to(torch.float32).reshape(1).contiguous()
+    ws = _workspace(dev, _lib.fn(dense + "_workspace_size")(P, Fd))
+    args = (P, Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n, *pair_args, g.data_ptr(),
+            plan.rowptr.data_ptr(), plan.ent.data_ptr(), plan.chunk_tab.data_ptr())
+    tail = (ws.data_ptr(), ws.numel(), _stream(hh))
+    others = (None,) * (len(ctx.needs_input_grad) - 1)
+    if ctx.leaf is not None and ctx.needs_input_grad[0]:
+        # a fuse_row_grad table: the touched rows' gradient goes to its optimizer, no
+        # (n, F) buffer is formed and .grad stays None
+        _stash_rows(ctx.leaf, plan, lambda *rows_vals: _lib.call(rows, *args, *rows_vals, *tail))
+        return (None,) + others
+    dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
+    _lib.call(dense, *args, dH.data_ptr(), *tail)
+    return (_table_grad(dH, ctx.dt),) + others
+
+
 class _LinkBCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, src, dst, target, weight, plan):
         dt = h.dtype
-        hh = h.detach()
-        esz = hh.element_size()
-        if not (hh.stride(1) == 1 and (hh.stride(0) * esz) % 16 == 0 and hh.data_ptr() % 16 == 0):
-            hh = hh.contiguous()
+        hh = _rows16(h.detach())
         n, Fd = hh.shape
         P, dev, s = src.numel(), hh.device, _stream(hh)
         z = torch.empty(P, dtype=torch.float32, device=dev)
@@ -1765,24 +1836,9 @@ class _LinkBCE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, _gz=None, _gpad=None):
         hh, src, dst, target, weight, z = ctx.saved_tensors
-        n, Fd = hh.shape
-        P, dev = src.numel(), hh.device
-        plan = ctx.plan
-        g = gloss.detach().to(torch.float32).reshape(1).contiguous()
-        ws = _workspace(dev, _lib.fn("msha_link_bce_bwd_workspace_size")(P, Fd))
-        args = (P, Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n, src.data_ptr(),
-                dst.data_ptr(), target.data_ptr(), _lib.ptr(weight), z.data_ptr(), g.data_ptr(),
-                plan.rowptr.data_ptr(), plan.ent.data_ptr(), plan.chunk_tab.data_ptr())
-        tail = (ws.data_ptr(), ws.numel(), _stream(hh))
-        if ctx.leaf is not None and ctx.needs_input_grad[0]:
-            # a fuse_row_grad table: the touched rows' gradient goes to its optimizer, no
-            # (n, F) buffer is formed and .grad stays None
-            _stash_rows(ctx.leaf, plan, lambda *rows_vals: _lib.call(
-                "msha_link_bce_bwd_rows", *args, *rows_vals, *tail))
-            return None, None, None, None, None, None
-        dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
-        _lib.call("msha_link_bce_bwd", *args, dH.data_ptr(), *tail)
-        return (dH if ctx.dt == torch.float32 else dH.to(ctx.dt)), None, None, None, None, None
+        return _pair_grad_backward(
+            ctx, gloss, hh, "msha_link_bce_bwd", "msha_link_bce_bwd_rows",
+            (src.data_ptr(), dst.data_ptr(), target.data_ptr(), _lib.ptr(weight), z.data_ptr()))
 
 
 def link_bce_loss(h, src, dst, target, weight=None, plan=None, return_logits=False):
@@ -1803,10 +1859,8 @@ def link_bce_loss(h, src, dst, target, weight=None, plan=None, return_logits=Fal
     when None; reuse it for as long as the pair list is unchanged) with no float atomics:
     bitwise reproducible.  Nothing (P, F)-sized is materialised and nothing is read back, so
     plan + loss + backward can be captured into one HIP graph."""
-    if h.dtype not in (torch.float32, BF16):
-        raise TypeError(f"link_bce_loss takes a float32 or bfloat16 table, got {h.dtype}")
-    if h.dim() != 2:
-        raise ValueError(f"link_bce_loss: h must be (n, F), got {tuple(h.shape)}")
+    _check_table_dtype("link_bce_loss", h)
+    _check_table_shape("link_bce_loss", h)
     _pair_lists(src, dst, "link_bce_loss")
     P = src.numel()
     if P < 1 or h.shape[0] < 1:
@@ -1817,15 +1871,9 @@ def link_bce_loss(h, src, dst, target, weight=None, plan=None, return_logits=Fal
     if weight is not None and (not weight.is_floating_point() or weight.shape != (P,)):
         raise ValueError(f"link_bce_loss: weight must be a float tensor of shape ({P},), got "
                          f"{weight.dtype} {tuple(weight.shape)}")
-    if plan is not None and (not isinstance(plan, PairPlan) or plan.n != h.shape[0]
-                             or plan.n_pairs != P):
-        raise ValueError("link_bce_loss: plan is not a PairPlan of this pair list and table")
-    if not _lib.fn("msha_link_bce_supported")(h.shape[1], _code(h.dtype)):
-        raise ValueError(f"link_bce_loss: feature width {h.shape[1]} of a {h.dtype} table is "
-                         f"not supported (a power of two, 16 bytes to 64 lanes x 16 bytes)")
-    for t in (src, dst, target, weight):
-        if t is not None and t.device != h.device:
-            raise ValueError("link_bce_loss: every tensor must be on the table's device")
+    _check_plan("link_bce_loss", plan, h.shape[0], P)
+    _check_table_width("link_bce_loss", h)
+    _check_same_device("link_bce_loss", h, src, dst, target, weight)
     _lib.require_cuda(h)
     target = target.detach().to(torch.float32).contiguous()
     weight = weight.detach().to(torch.float32).contiguous() if weight is not None else None
@@ -1840,10 +1888,7 @@ class _LinkMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, W, b, src, dst, label, teacher, w_label, w_mse, p, seed, plan):
         dt = h.dtype
-        hh = h.detach()
-        esz = hh.element_size()
-        if not (hh.stride(1) == 1 and (hh.stride(0) * esz) % 16 == 0 and hh.data_ptr() % 16 == 0):
-            hh = hh.contiguous()
+        hh = _rows16(h.detach())
         n, Fd = hh.shape
         N = W.shape[0]
         Wk = _tc(W.detach(), dt)  # the kernel's weight: bf16 for a bf16 table (score_pairs)
@@ -1896,8 +1941,8 @@ class _LinkMLP(torch.autograd.Function):
                   _lib.ptr(plan.chunk_tab if need_h else None), dz.data_ptr(), _lib.ptr(dx),
                   _lib.ptr(dW), _lib.ptr(db), _lib.ptr(dH), ws.data_ptr(), ws.numel(),
                   _stream(hh))
-        if need_h and ctx.dt != torch.float32:
-            dH = dH.to(ctx.dt)
+        if need_h:
+            dH = _table_grad(dH, ctx.dt)
         if need_w:
             dW = dW if ctx.wdt == torch.float32 else dW.to(ctx.wdt)
             db = db if ctx.bdt == torch.float32 else db.to(ctx.bdt)
@@ -1931,10 +1976,8 @@ def link_mlp_loss(h, src, dst, W, b, *, label=None, teacher_out=None, w_label=1.
     (``pair_plan(src, dst, n)``, built here when None and ``h`` needs a gradient; reuse it
     for as long as the pair list is unchanged).  No float atomics: bitwise reproducible.
     Nothing is read back, so plan + loss + backward can be captured into one HIP graph."""
-    if h.dtype not in (torch.float32, BF16):
-        raise TypeError(f"link_mlp_loss takes a float32 or bfloat16 table, got {h.dtype}")
-    if h.dim() != 2:
-        raise ValueError(f"link_mlp_loss: h must be (n, F), got {tuple(h.shape)}")
+    _check_table_dtype("link_mlp_loss", h)
+    _check_table_shape("link_mlp_loss", h)
     _pair_lists(src, dst, "link_mlp_loss")
     P, Fd = src.numel(), h.shape[1]
     if P < 1 or h.shape[0] < 1:
@@ -1956,15 +1999,11 @@ def link_mlp_loss(h, src, dst, W, b, *, label=None, teacher_out=None, w_label=1.
     p = float(p) if training else 0.0
     if not 0.0 <= p < 1.0:
         raise ValueError(f"link_mlp_loss: p must be in [0, 1), got {p}")
-    if plan is not None and (not isinstance(plan, PairPlan) or plan.n != h.shape[0]
-                             or plan.n_pairs != P):
-        raise ValueError("link_mlp_loss: plan is not a PairPlan of this pair list and table")
+    _check_plan("link_mlp_loss", plan, h.shape[0], P)
     if not _lib.fn("msha_link_mlp_supported")(Fd, N, _code(h.dtype)):
         raise ValueError(f"link_mlp_loss: widths F = {Fd}, N = {N} of a {h.dtype} table are not "
                          f"supported (powers of two in [16, 128])")
-    for t in (src, dst, W, b, label, teacher_out):
-        if t is not None and t.device != h.device:
-            raise ValueError("link_mlp_loss: every tensor must be on the table's device")
+    _check_same_device("link_mlp_loss", h, src, dst, W, b, label, teacher_out)
     _lib.require_cuda(h)
     src, dst = src.contiguous(), dst.contiguous()
     label = label.contiguous() if label is not None else None
@@ -2066,18 +2105,12 @@ class _LinkDistill(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, anchors, context, tl, th, margin, tau, w_rank, w_dist, w_prob, plan):
         dt = h.dtype
-
-        def aligned(t):
-            esz = t.element_size()
-            ok = t.stride(1) == 1 and (t.stride(0) * esz) % 16 == 0 and t.data_ptr() % 16 == 0
-            return t if ok else t.contiguous()
-
-        hh = aligned(h.detach())
+        hh = _rows16(h.detach())
         n, Fd = hh.shape
         A, K = context.shape
         dev, s = hh.device, _stream(hh)
         if th is not None:
-            th = aligned(th)
+            th = _rows16(th)
             t_args = (th.data_ptr(), th.shape[1], _code(th.dtype), th.stride(0), th.shape[0])
         else:
             t_args = (None, 0, 0, 0, 0)
@@ -2100,22 +2133,9 @@ class _LinkDistill(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, _gt=None, _gz=None, _gpad=None):
         hh, context, g = ctx.saved_tensors
-        n, Fd = hh.shape
-        P, dev = context.numel(), hh.device
-        plan = ctx.plan
-        gl = gloss.detach().to(torch.float32).reshape(1).contiguous()
-        ws = _workspace(dev, _lib.fn("msha_pair_grad_bwd_workspace_size")(P, Fd))
-        args = (P, Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n, plan.src.data_ptr(),
-                context.data_ptr(), g.data_ptr(), gl.data_ptr(), plan.rowptr.data_ptr(),
-                plan.ent.data_ptr(), plan.chunk_tab.data_ptr())
-        tail = (ws.data_ptr(), ws.numel(), _stream(hh))
-        if ctx.leaf is not None and ctx.needs_input_grad[0]:  # a fuse_row_grad table
-            _stash_rows(ctx.leaf, plan, lambda *rows_vals: _lib.call(
-                "msha_pair_grad_bwd_rows", *args, *rows_vals, *tail))
-            return (None,) * 11
-        dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
-        _lib.call("msha_pair_grad_bwd", *args, dH.data_ptr(), *tail)
-        return ((dH if ctx.dt == torch.float32 else dH.to(ctx.dt)),) + (None,) * 10
+        return _pair_grad_backward(
+            ctx, gloss, hh, "msha_pair_grad_bwd", "msha_pair_grad_bwd_rows",
+            (ctx.plan.src.data_ptr(), context.data_ptr(), g.data_ptr()))
 
 
 def link_distill_loss(h, anchors, context, *, teacher_logits=None, teacher_table=None,
@@ -2143,10 +2163,8 @@ def link_distill_loss(h, anchors, context, *, teacher_logits=None, teacher_table
     (``context_plan(anchors, context, n)``, built here when None and a gradient is needed)
     with no float atomics: bitwise reproducible, nothing (A, K, F)-sized is materialised and
     nothing is read back, so sample + plan + loss + backward capture into one HIP graph."""
-    if h.dtype not in (torch.float32, BF16):
-        raise TypeError(f"link_distill_loss takes a float32 or bfloat16 table, got {h.dtype}")
-    if h.dim() != 2:
-        raise ValueError(f"link_distill_loss: h must be (n, F), got {tuple(h.shape)}")
+    _check_table_dtype("link_distill_loss", h)
+    _check_table_shape("link_distill_loss", h)
     _context_lists(anchors, context, "link_distill_loss")
     A, K = context.shape
     if A < 1 or h.shape[0] < 1:
@@ -2161,29 +2179,17 @@ def link_distill_loss(h, anchors, context, *, teacher_logits=None, teacher_table
         raise ValueError(f"link_distill_loss: teacher_logits must be a float tensor of shape "
                          f"({A}, {K}), got {teacher_logits.dtype} {tuple(teacher_logits.shape)}")
     if teacher_table is not None:
-        if teacher_table.dtype not in (torch.float32, BF16):
-            raise TypeError(f"link_distill_loss takes a float32 or bfloat16 teacher table, got "
-                            f"{teacher_table.dtype}")
-        if teacher_table.dim() != 2 or teacher_table.shape[0] < 1:
-            raise ValueError(f"link_distill_loss: teacher_table must be (n_t, F_t), got "
-                             f"{tuple(teacher_table.shape)}")
+        _check_table_dtype("link_distill_loss", teacher_table, "teacher table")
+        _check_table_shape("link_distill_loss", teacher_table, "teacher_table", "(n_t, F_t)",
+                           rows=True)
     margin, tau = float(margin), float(tau)
     if not tau > 0.0:
         raise ValueError(f"link_distill_loss: tau must be positive, got {tau}")
     if not margin >= 0.0:
         raise ValueError(f"link_distill_loss: margin must not be negative, got {margin}")
-    if plan is not None and (not isinstance(plan, PairPlan) or plan.n != h.shape[0]
-                             or plan.n_pairs != A * K or getattr(plan, "src", None) is None):
-        raise ValueError("link_distill_loss: plan is not a context_plan of this context and "
-                         "table")
-    for t in (h, teacher_table):
-        if t is not None and not _lib.fn("msha_link_bce_supported")(t.shape[1], _code(t.dtype)):
-            raise ValueError(f"link_distill_loss: feature width {t.shape[1]} of a {t.dtype} "
-                             f"table is not supported (a power of two, 16 bytes to 64 lanes x "
-                             f"16 bytes)")
-    for t in (anchors, context, teacher_logits, teacher_table):
-        if t is not None and t.device != h.device:
-            raise ValueError("link_distill_loss: every tensor must be on the table's device")
+    _check_plan("link_distill_loss", plan, h.shape[0], A * K, context=True)
+    _check_table_width("link_distill_loss", h, teacher_table)
+    _check_same_device("link_distill_loss", h, anchors, context, teacher_logits, teacher_table)
     _lib.require_cuda(h)
     anchors, context = anchors.contiguous(), context.contiguous()
     tl = (teacher_logits.detach().to(torch.float32).contiguous()
@@ -2198,14 +2204,6 @@ def link_distill_loss(h, anchors, context, *, teacher_logits=None, teacher_table
 
 
 # ------------------------------------------------------ representation matching ---
-def _rows16(t):
-    """``t`` itself when the kernels can read it in place (unit column stride, 16-byte row
-    pitch and base), else a contiguous copy."""
-    esz = t.element_size()
-    ok = t.stride(1) == 1 and (t.stride(0) * esz) % 16 == 0 and t.data_ptr() % 16 == 0
-    return t if ok else t.contiguous()
-
-
 class _LinkMatch(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, rows, th):
@@ -2238,7 +2236,7 @@ class _LinkMatch(torch.autograd.Function):
         _lib.call("msha_link_match_bwd", Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n,
                   _code(th.dtype), th.data_ptr(), th.stride(0), th.shape[0], coef.data_ptr(),
                   g.data_ptr(), dH.data_ptr(), _stream(hh))
-        return (dH if ctx.dt == torch.float32 else dH.to(ctx.dt)), None, None
+        return _table_grad(dH, ctx.dt), None, None
 
 
 def link_match_loss(h, rows, teacher_table, *, return_rows=False):
@@ -2263,16 +2261,10 @@ def link_match_loss(h, rows, teacher_table, *, return_rows=False):
     of ``rows`` -- with no float atomics, nothing (P, F)-sized and nothing read back, so
     loss + backward can be captured into one HIP graph."""
     t = teacher_table
-    if h.dtype not in (torch.float32, BF16):
-        raise TypeError(f"link_match_loss takes a float32 or bfloat16 table, got {h.dtype}")
-    if t.dtype not in (torch.float32, BF16):
-        raise TypeError(f"link_match_loss takes a float32 or bfloat16 teacher table, got "
-                        f"{t.dtype}")
-    if h.dim() != 2 or h.shape[0] < 1:
-        raise ValueError(f"link_match_loss: h must be (n, F), got {tuple(h.shape)}")
-    if t.dim() != 2 or t.shape[0] < 1:
-        raise ValueError(f"link_match_loss: teacher_table must be (n_t, F), got "
-                         f"{tuple(t.shape)}")
+    _check_table_dtype("link_match_loss", h)
+    _check_table_dtype("link_match_loss", t, "teacher table")
+    _check_table_shape("link_match_loss", h, rows=True)
+    _check_table_shape("link_match_loss", t, "teacher_table", "(n_t, F)", rows=True)
     if t.shape[1] != h.shape[1]:
         raise ValueError(f"link_match_loss: student and teacher must have one width, got "
                          f"{h.shape[1]} and {t.shape[1]}")
@@ -2285,14 +2277,8 @@ def link_match_loss(h, rows, teacher_table, *, return_rows=False):
     elif t.shape[0] != h.shape[0]:
         raise ValueError(f"link_match_loss: rows=None needs equal row counts, got "
                          f"{h.shape[0]} and {t.shape[0]}")
-    for x in (h, t):
-        if not _lib.fn("msha_link_bce_supported")(x.shape[1], _code(x.dtype)):
-            raise ValueError(f"link_match_loss: feature width {x.shape[1]} of a {x.dtype} table "
-                             f"is not supported (a power of two, 16 bytes to 64 lanes x 16 "
-                             f"bytes)")
-    for x in (rows, t):
-        if x is not None and x.device != h.device:
-            raise ValueError("link_match_loss: every tensor must be on the table's device")
+    _check_table_width("link_match_loss", h, t)
+    _check_same_device("link_match_loss", h, rows, t)
     _lib.require_cuda(h)
     rows = rows.contiguous() if rows is not None else None
     loss, cos_rows, count, _ = _LinkMatch.apply(h, rows, t.detach())

@@ -16,8 +16,9 @@ The two are timed in alternating rounds (median of 7 rounds of HIP-event times p
 warm-up).  Also, through the ABI: the forward call and its MFMA launch alone (their difference
 is the index pass + loss pass + finish); the backward with only dz, with dz + weight
 gradient, and whole, and ``dx = dz W`` alone -- the weight-gradient and table-gradient times
-are differences of those.  Each with the achieved fraction of the 8 TB/s HBM peak by its byte
-model.  The plan build is timed on its own.
+are differences of those (``table_grad_round_us``: the table-gradient difference of each
+round, to show how far that column repeats).  Each with the achieved fraction of the 8 TB/s
+HBM peak by its byte model.  The plan build is timed on its own.
 
 Every configuration runs as a child process under its own time limit; the first child that
 fails ends the run.  Prints one JSON object and writes it out.
@@ -44,15 +45,18 @@ W_LABEL, W_MSE = 10.0, 100.0
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16}
 
 
-def alternate_us(fns, rounds=ROUNDS, reps=3):
+def alternate_us(fns, rounds=ROUNDS, reps=3, keep=None):
     """Median over ``rounds`` of the per-call time of each function, the functions taking
-    turns inside every round."""
+    turns inside every round.  ``keep``: a list that receives the rounds' own times, one list
+    per function."""
     from gemm_ab import timeit
 
     times = [[] for _ in fns]
     for _ in range(rounds):
         for k, fn in enumerate(fns):
             times[k].append(timeit(fn, reps=reps, warm=2))
+    if keep is not None:
+        keep.extend(times)
     return [float(np.median(t)) for t in times]
 
 
@@ -153,8 +157,10 @@ def step_case(name, dist):
     t_f, t_b = alternate_us([fused, baseline])
     fwd_call()
     t_fw, t_mm = alternate_us([fwd_call, mfma_only], reps=5)
+    bwd_rounds = []
     t_dz, t_dzw, t_all, t_dx = alternate_us([bwd_call(False, False), bwd_call(True, False),
-                                             bwd_call(True, True), dx_only], reps=5)
+                                             bwd_call(True, True), dx_only], reps=5,
+                                            keep=bwd_rounds)
     (t_plan,) = alternate_us([lambda: MF.pair_plan(src, dst, n)], reps=5)
     esz = 4 if dt == torch.float32 else 2
     blocks = -(-P // lib.msha_link_mlp_wgrad_rows())
@@ -172,7 +178,9 @@ def step_case(name, dist):
            "fwd_call_us": round(t_fw, 1), "fwd_mfma_launch_us": round(t_mm, 1),
            "bwd_call_us": round(t_all, 1), "dx_gemm_us": round(t_dx, 1),
            "plan_build_us": round(t_plan, 1),
-           "fused_gradients_bitwise_repeatable": again, "loss_fused": l_f, "loss_torch": l_b}
+           "fused_gradients_bitwise_repeatable": again, "loss_fused": l_f, "loss_torch": l_b,
+           # the table-gradient difference round by round: how far the column repeats
+           "table_grad_round_us": [round(a - w - x, 1) for _, w, a, x in zip(*bwd_rounds)]}
     for k in model:
         res[f"{k}_us"] = round(times[k], 1)
         res[f"{k}_model_bytes"] = model[k]
