@@ -1176,6 +1176,27 @@ MSHA_API int msha_link_bce_bwd_rows(int64_t n_pairs, int32_t feat, int32_t dtype
                                     const int32_t* rows, const int32_t* n_rows, int64_t cap,
                                     float* vals, void* ws, size_t ws_bytes,
                                     msha_stream_t stream); /* (ABI 16, added) */
+/* The sum of k row gradients of one (n, feat) table (ABI 16, added), 1 <= k <= 4.  List j: rows
+ * int32 (cap_j, 1 <= cap_j <= n) ascending and distinct with -1 past its DEVICE count n_rows[0],
+ * vals (cap_j, feat) fp32, 16-byte aligned.  Output: rows (cap = min(n, sum of cap_j)) the
+ * ascending union, -1 past the count; n_rows[0] the count, a DEVICE int32; vals (cap, feat)
+ * fp32, 16-byte aligned, vals[i] = x_1 + x_2 + .. + x_k added left to right in fp32, x_j the
+ * row's value in list j or +0.0 where list j does not hold it (what accumulating k dense fp32
+ * gradients gives, signed zeros included); zeros past the count.  The lists' rows are marked
+ * in n ints, which go through msha_plan_rows' scan and compaction; each output row then finds
+ * itself in each sorted list.  Integer compares, no atomics, nothing read back.  feat a
+ * multiple of 4.  ws: msha_row_grad_union_workspace_size(n) bytes, 16-byte aligned. */
+typedef struct msha_row_list {
+  const int32_t* rows;
+  const int32_t* n_rows;
+  int64_t cap;
+  const float* vals;
+} msha_row_list;
+MSHA_API size_t msha_row_grad_union_workspace_size(int64_t n); /* (ABI 16, added) */
+MSHA_API int msha_row_grad_union(int64_t n, int32_t feat, int32_t k, const msha_row_list* lists,
+                                 int32_t* rows, int32_t* n_rows, int64_t cap, float* vals,
+                                 void* ws, size_t ws_bytes,
+                                 msha_stream_t stream); /* (ABI 16, added) */
 
 /* ---- Link-prediction distillation for the inner-product scorer (LLP.py:231-238: a
  * teacher-matching term added to the label loss) (ABI 16, added) ------------------------
@@ -1288,6 +1309,22 @@ MSHA_API int msha_link_match_bwd(int32_t feat, int32_t h_dtype, const void* h, i
                                  int64_t n, int32_t t_dtype, const void* teacher, int64_t t_ld,
                                  int64_t n_t, const float* coef, const float* gloss, float* dH,
                                  msha_stream_t stream); /* (ABI 16, added) */
+/* The list of the rows that occur (ABI 16, added): rows int32, capacity cap = min(n,
+ * n_entries), the ascending r with count[r] > 0 (the forward's count), -1 past the count;
+ * n_rows[0] the count, a DEVICE int32.  msha_plan_rows' three launches over another flag;
+ * ws: msha_plan_rows_workspace_size(n) bytes, 16-byte aligned.  n < 2^31 - 1. */
+MSHA_API int msha_link_match_rows(int64_t n_entries, int64_t n, const int32_t* count,
+                                  int32_t* rows, int32_t* n_rows, void* ws, size_t ws_bytes,
+                                  msha_stream_t stream); /* (ABI 16, added) */
+/* msha_link_match_bwd for the rows of that list only (ABI 16, added): vals (cap, feat) fp32,
+ * 16-byte aligned, vals[i] bit for bit msha_link_match_bwd's dH[rows[i]] (the same per-row
+ * formula) for i < n_rows[0], zeros from there to cap.  cap must be min(n, n_entries). */
+MSHA_API int msha_link_match_bwd_rows(int64_t n_entries, int32_t feat, int32_t h_dtype,
+                                      const void* h, int64_t ld, int64_t n, int32_t t_dtype,
+                                      const void* teacher, int64_t t_ld, int64_t n_t,
+                                      const float* coef, const float* gloss, const int32_t* rows,
+                                      const int32_t* n_rows, int64_t cap, float* vals,
+                                      msha_stream_t stream); /* (ABI 16, added) */
 
 /* ---- Link-prediction training of the 'mlp' predictor with one used Linear (LLP.py:233,
  * :235, :238) (ABI 16, added) ------------------------------------------------------------
@@ -1341,6 +1378,22 @@ MSHA_API int msha_link_mlp_bwd(int64_t n_pairs, int32_t feat, int32_t hidden, in
                                const int32_t* plan_ent, const int32_t* plan_chunk_tab, float* dz,
                                float* dx, float* dW, float* db, float* dH, void* ws,
                                size_t ws_bytes, msha_stream_t stream); /* (ABI 16, added) */
+/* msha_link_mlp_bwd with the table gradient on the rows of the plan's touched-row list only
+ * (ABI 16, added): dz, dx, dW and db as above; vals (cap, feat) fp32, 16-byte aligned, vals[i]
+ * bit for bit what msha_link_mlp_bwd writes to dH[rows[i]] for i < n_rows[0], zeros from there
+ * to cap.  rows, n_rows from msha_plan_rows of the same plan; cap must be min(n, 2 n_pairs).
+ * The same workspace. */
+MSHA_API int msha_link_mlp_bwd_rows(int64_t n_pairs, int32_t feat, int32_t hidden, int32_t dtype,
+                                    const void* h, int64_t ld, int64_t n, const int64_t* src,
+                                    const int64_t* dst, const int64_t* label, const float* W32,
+                                    const float* teacher_out, const float* out,
+                                    const int32_t* n_valid, float w_label, float w_mse,
+                                    float drop_p, const float* gloss, const int32_t* plan_rowptr,
+                                    const int32_t* plan_ent, const int32_t* plan_chunk_tab,
+                                    float* dz, float* dx, float* dW, float* db,
+                                    const int32_t* rows, const int32_t* n_rows, int64_t cap,
+                                    float* vals, void* ws, size_t ws_bytes,
+                                    msha_stream_t stream); /* (ABI 16, added) */
 
 /* ---- The GraphSAGE baseline on sparse adjacency rows (SGAE.py:41-56) (ABI 16, added) ------
  *   x = table[src]  (B, in);  z1 = relu(x W1^T + b1)  (B, M);  y = adj[src] * z1  (hidden == M);
@@ -1384,6 +1437,23 @@ MSHA_API int msha_sage_bwd(const msha_graph* g, int64_t B, const int64_t* src, i
                            const float* logp, const float* dlogp, float* dS, float* dW1,
                            float* db1, float* dW2, float* db2, void* ws, size_t ws_bytes,
                            msha_stream_t stream); /* (ABI 16, added) */
+/* msha_sage_bwd with the table gradient on the rows of the batch only (ABI 16, added): the same
+ * row pass, weight gradients and (src, src) plan, then msha_plan_rows of that plan into rows
+ * (cap = min(n, 2 B) int32) and n_rows (a DEVICE int32): the ascending distinct sources inside
+ * [0, n), -1 past the count.  row_vals (cap, in) fp32, 16-byte aligned: row_vals[i] bit for bit
+ * what msha_sage_bwd writes to dS[rows[i]] (the same entries in the same order), exact zeros
+ * past the count.  rows, n_rows and row_vals are OUTPUTS; rows and row_vals may be NULL when
+ * cap is 0.  ws: msha_sage_rows_workspace_size bytes (msha_sage_workspace_size plus
+ * msha_plan_rows' workspace), 16-byte aligned. */
+MSHA_API size_t msha_sage_rows_workspace_size(int64_t B, int64_t n, int32_t in, int32_t M,
+                                              int32_t out); /* (ABI 16, added) */
+MSHA_API int msha_sage_bwd_rows(const msha_graph* g, int64_t B, const int64_t* src, int32_t in,
+                                int32_t out, const float* table, int64_t ld, const float* vals,
+                                const float* W1, const float* b1, const float* W2, const float* b2,
+                                const float* logp, const float* dlogp, float* dW1, float* db1,
+                                float* dW2, float* db2, int32_t* rows, int32_t* n_rows,
+                                int64_t cap, float* row_vals, void* ws, size_t ws_bytes,
+                                msha_stream_t stream); /* (ABI 16, added) */
 
 #ifdef __cplusplus
 }

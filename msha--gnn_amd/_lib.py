@@ -84,6 +84,16 @@ class MshaAdamTensor(C.Structure):
 
 
 
+class MshaRowList(C.Structure):
+    """Mirror of ``struct msha_row_list`` (include/msha_gnn.h)."""
+
+    _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_void_p), ("cap", C.c_int64),
+                ("vals", C.c_void_p)]
+
+
+MAX_ROW_LISTS = 4
+
+
 class MshaSegment(C.Structure):
     """Mirror of ``struct msha_segment`` (include/msha_gnn.h)."""
 
@@ -290,6 +300,14 @@ SIGNATURES = {
                                          P, P, I64, P, P, SZ, P]),
     "msha_pair_grad_bwd_rows": (C.c_int, [I64, I32, I32, P, I64, I64, P, P, P, P, P, P, P, P, P,
                                           I64, P, P, SZ, P]),
+    "msha_link_mlp_bwd_rows": (C.c_int, [I64, I32, I32, I32, P, I64, I64, P, P, P, P, P, P, P, F32,
+                                         F32, F32, P, P, P, P, P, P, P, P, P, P, I64, P, P, SZ,
+                                         P]),
+    "msha_link_match_rows": (C.c_int, [I64, I64, P, P, P, P, SZ, P]),
+    "msha_link_match_bwd_rows": (C.c_int, [I64, I32, I32, P, I64, I64, I32, P, I64, I64, P, P, P,
+                                           P, I64, P, P]),
+    "msha_row_grad_union_workspace_size": (SZ, [I64]),
+    "msha_row_grad_union": (C.c_int, [I64, I32, I32, P, P, P, I64, P, P, SZ, P]),
     "msha_adam_rows_step": (C.c_int, [I64, I32, I32, P, P, P, P, P, P, I64, P, C.c_double,
                                       C.c_double, C.c_double, C.c_double, P]),
     # GraphSAGE baseline on sparse adjacency rows (ABI 16, added)
@@ -298,6 +316,9 @@ SIGNATURES = {
     "msha_sage_fwd": (C.c_int, [GP, I64, P, I32, I32, P, I64, P, P, P, P, P, P, P]),
     "msha_sage_bwd": (C.c_int, [GP, I64, P, I32, I32, P, I64, P, P, P, P, P, P, P, P, P, P, P,
                                 P, P, SZ, P]),
+    "msha_sage_rows_workspace_size": (SZ, [I64, I64, I32, I32, I32]),
+    "msha_sage_bwd_rows": (C.c_int, [GP, I64, P, I32, I32, P, I64, P, P, P, P, P, P, P, P, P, P,
+                                     P, P, P, I64, P, P, SZ, P]),
 }
 
 _lib = None

@@ -527,31 +527,35 @@ extern "C" int msha_link_mlp_loss_fwd(int64_t n_pairs, int32_t feat, int32_t hid
   return check_launch("link_mlp_loss_fwd");
 }
 
-extern "C" int msha_link_mlp_bwd(int64_t n_pairs, int32_t feat, int32_t hidden, int32_t dtype,
-                                 const void* h, int64_t ld, int64_t n, const int64_t* src,
-                                 const int64_t* dst, const int64_t* label, const float* W32,
-                                 const float* teacher_out, const float* out,
-                                 const int32_t* n_valid, float w_label, float w_mse, float drop_p,
-                                 const float* gloss, const int32_t* plan_rowptr,
-                                 const int32_t* plan_ent, const int32_t* plan_chunk_tab,
-                                 float* dz, float* dx, float* dW, float* db, float* dH, void* ws,
-                                 size_t ws_bytes, msha_stream_t stream) {
-  const int rc = lm_check("link_mlp_bwd", n_pairs, feat, hidden, dtype, h, ld, n);
+namespace msha {
+
+// msha_link_mlp_bwd and msha_link_mlp_bwd_rows: out = dH (n, F) with PgAllRows, the (cap, F)
+// vals of the touched-row list with PgListRows; everything before the table gradient is shared
+template <typename R>
+static int lm_bwd_run(const char* name, int64_t n_pairs, int32_t feat, int32_t hidden,
+                      int32_t dtype, const void* h, int64_t ld, int64_t n, const int64_t* src,
+                      const int64_t* dst, const int64_t* label, const float* W32,
+                      const float* teacher_out, const float* out, const int32_t* n_valid,
+                      float w_label, float w_mse, float drop_p, const float* gloss,
+                      const int32_t* plan_rowptr, const int32_t* plan_ent,
+                      const int32_t* plan_chunk_tab, float* dz, float* dx, float* dW, float* db,
+                      float* dH, void* ws, size_t ws_bytes, msha_stream_t stream, R rows) {
+  const std::string nm(name);
+  const int rc = lm_check(name, n_pairs, feat, hidden, dtype, h, ld, n);
   if (rc != MSHA_OK) return rc;
-  MSHA_ARG_CHECK(src && dst && out && n_valid && gloss && dz, "link_mlp_bwd: null pointer");
+  MSHA_ARG_CHECK(src && dst && out && n_valid && gloss && dz, nm + ": null pointer");
   MSHA_ARG_CHECK((dW == nullptr) == (db == nullptr),
-                 "link_mlp_bwd: dW and db come together or not at all");
+                 nm + ": dW and db come together or not at all");
   MSHA_ARG_CHECK(dH == nullptr || (W32 && dx && plan_rowptr && plan_ent && plan_chunk_tab),
-                 "link_mlp_bwd: dH needs W, dx and the plan");
-  MSHA_ARG_CHECK(drop_p >= 0.f && drop_p < 1.f, "link_mlp_bwd: drop_p must be in [0, 1)");
+                 nm + ": " + R::kOut + " needs W, dx and the plan");
+  MSHA_ARG_CHECK(drop_p >= 0.f && drop_p < 1.f, nm + ": drop_p must be in [0, 1)");
   MSHA_ARG_CHECK(((uintptr_t)out % 16) == 0 && ((uintptr_t)dz % 16) == 0 &&
                      ((uintptr_t)dx % 16) == 0 && ((uintptr_t)dH % 16) == 0 &&
                      (teacher_out == nullptr || ((uintptr_t)teacher_out % 16) == 0),
-                 "link_mlp_bwd: out, teacher_out, dz, dx and dH must be 16-byte aligned");
+                 nm + ": out, teacher_out, dz, dx and " + R::kOut + " must be 16-byte aligned");
   const LmBwdLayout L = lm_bwd_layout(n_pairs, feat, hidden);
   MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= L.total && ((uintptr_t)ws % 16) == 0,
-                 "link_mlp_bwd: workspace too small or unaligned "
-                 "(msha_link_mlp_bwd_workspace_size)");
+                 nm + ": workspace too small or unaligned (msha_link_mlp_bwd_workspace_size)");
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)ws;
   const int F = feat, N = hidden;
@@ -575,9 +579,47 @@ extern "C" int msha_link_mlp_bwd(int64_t n_pairs, int32_t feat, int32_t hidden, 
                                   stream);
     if (grc != MSHA_OK) return grc;
     // dH from dx under the plan (pair_grad.h); dx carries gloss already (lm_dz_kernel)
-    return pg_run("link_mlp_bwd", "msha_link_mlp_bwd_workspace_size", n_pairs, feat, dtype, h, ld,
-                  n, src, dst, plan_rowptr, plan_ent, plan_chunk_tab, PgDx{dx}, nullptr, dH,
-                  w + L.pgpart, L.total - L.pgpart, stream, PgAllRows{});
+    return pg_run(name, "msha_link_mlp_bwd_workspace_size", n_pairs, feat, dtype, h, ld, n, src,
+                  dst, plan_rowptr, plan_ent, plan_chunk_tab, PgDx{dx}, nullptr, dH, w + L.pgpart,
+                  L.total - L.pgpart, stream, rows);
   }
-  return check_launch("link_mlp_bwd");
+  return check_launch(name);
+}
+
+}  // namespace msha
+
+extern "C" int msha_link_mlp_bwd(int64_t n_pairs, int32_t feat, int32_t hidden, int32_t dtype,
+                                 const void* h, int64_t ld, int64_t n, const int64_t* src,
+                                 const int64_t* dst, const int64_t* label, const float* W32,
+                                 const float* teacher_out, const float* out,
+                                 const int32_t* n_valid, float w_label, float w_mse, float drop_p,
+                                 const float* gloss, const int32_t* plan_rowptr,
+                                 const int32_t* plan_ent, const int32_t* plan_chunk_tab,
+                                 float* dz, float* dx, float* dW, float* db, float* dH, void* ws,
+                                 size_t ws_bytes, msha_stream_t stream) {
+  return lm_bwd_run("link_mlp_bwd", n_pairs, feat, hidden, dtype, h, ld, n, src, dst, label, W32,
+                    teacher_out, out, n_valid, w_label, w_mse, drop_p, gloss, plan_rowptr,
+                    plan_ent, plan_chunk_tab, dz, dx, dW, db, dH, ws, ws_bytes, stream,
+                    PgAllRows{});
+}
+
+extern "C" int msha_link_mlp_bwd_rows(int64_t n_pairs, int32_t feat, int32_t hidden,
+                                      int32_t dtype, const void* h, int64_t ld, int64_t n,
+                                      const int64_t* src, const int64_t* dst,
+                                      const int64_t* label, const float* W32,
+                                      const float* teacher_out, const float* out,
+                                      const int32_t* n_valid, float w_label, float w_mse,
+                                      float drop_p, const float* gloss,
+                                      const int32_t* plan_rowptr, const int32_t* plan_ent,
+                                      const int32_t* plan_chunk_tab, float* dz, float* dx,
+                                      float* dW, float* db, const int32_t* rows,
+                                      const int32_t* n_rows, int64_t cap, float* vals, void* ws,
+                                      size_t ws_bytes, msha_stream_t stream) {
+  MSHA_ARG_CHECK(rows && n_rows && vals, "link_mlp_bwd_rows: null pointer");
+  MSHA_ARG_CHECK(cap == pg_rows_cap(n, n_pairs),
+                 "link_mlp_bwd_rows: cap must be min(n, 2 * n_pairs) (msha_plan_rows)");
+  return lm_bwd_run("link_mlp_bwd_rows", n_pairs, feat, hidden, dtype, h, ld, n, src, dst, label,
+                    W32, teacher_out, out, n_valid, w_label, w_mse, drop_p, gloss, plan_rowptr,
+                    plan_ent, plan_chunk_tab, dz, dx, dW, db, vals, ws, ws_bytes, stream,
+                    PgListRows{rows, n_rows, cap});
 }

@@ -24,6 +24,7 @@
 //   link_match_bwd   dH[r] = -gloss (coef[r, 0] T[r] - coef[r, 1] h[r]), one streaming pass.
 #include "common.h"
 #include "pair_grad.h"
+#include "row_list.h"
 
 // the histogram's form: 1 = equal indices aggregated in an LDS table per block, flushed
 // with one global add per distinct row; 0 = one global add per entry (A/B)
@@ -306,12 +307,14 @@ __global__ void __launch_bounds__(kMtFinThreads) mt_final_kernel(
 // -------------------------------------------------------------------- backward ----
 
 // dH[r] = -gloss (coef[r, 0] T[r] - coef[r, 1] h[r]); a row whose coefficients are both zero
-// (absent, or outside the teacher) is written as zeros and reads neither table
-template <typename TH, typename TT>
+// (absent, or outside the teacher) is written as zeros and reads neither table.  R (pair_grad.h):
+// every table row to dH[r] (PgAllRows), or entry i of the list of the rows that occur
+// (msha_link_match_rows) to vals[i] (PgListRows; zeros past the device count).
+template <typename TH, typename TT, typename R>
 __global__ void __launch_bounds__(kMtThreads) mt_bwd_kernel(
     int64_t n, int64_t n_t, int F, const TH* __restrict__ h, int64_t ld, const TT* __restrict__ T,
     int64_t t_ld, const float* __restrict__ coef, const float* __restrict__ gloss,
-    float* __restrict__ dH) {
+    float* __restrict__ dH, R rows) {
   constexpr int V = MtGeo<TH, TT>::V;
   constexpr int UNROLL = 4;
   const int lane = lane_id();
@@ -321,14 +324,16 @@ __global__ void __launch_bounds__(kMtThreads) mt_bwd_kernel(
   const int64_t m = n < n_t ? n : n_t;
   const int64_t wave = ((int64_t)blockIdx.x * kMtThreads + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * kMtThreads) >> 6;
-  for (int64_t r0 = wave * RPW * UNROLL; r0 < n; r0 += nwaves * RPW * UNROLL) {
+  const int64_t cnt = rows.count(n), ext = rows.extent(n);
+  for (int64_t i0 = wave * RPW * UNROLL; i0 < ext; i0 += nwaves * RPW * UNROLL) {
     float hv[UNROLL][V], tv[UNROLL][V];
     float2 cf[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-      const int64_t r = r0 + u * RPW + slot;
+      const int64_t i = i0 + u * RPW + slot;
+      const int64_t r = i < ext ? rows.row(i, cnt) : -1;
       cf[u] = make_float2(0.f, 0.f);
-      if (r < m) cf[u] = *reinterpret_cast<const float2*>(coef + 2 * r);
+      if ((uint64_t)r < (uint64_t)m) cf[u] = *reinterpret_cast<const float2*>(coef + 2 * r);
       const bool on = cf[u].x != 0.f || cf[u].y != 0.f;
       if (on) {
         MtRow<V, TH>::load(h + r * ld + V * q, hv[u]);
@@ -340,10 +345,10 @@ __global__ void __launch_bounds__(kMtThreads) mt_bwd_kernel(
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-      const int64_t r = r0 + u * RPW + slot;
-      if (r >= n) continue;
+      const int64_t i = i0 + u * RPW + slot;
+      if (i >= ext) continue;
       const bool on = cf[u].x != 0.f || cf[u].y != 0.f;
-      float* out = dH + r * F + V * q;
+      float* out = dH + i * F + V * q;
 #pragma unroll
       for (int k = 0; k < V; k += 4) {
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -399,16 +404,22 @@ static void mt_rows_launch(const MtArgs& a, const void* h, const void* T, int64_
                      (const TH*)h, (const TT*)T);
 }
 
-template <typename TH, typename TT>
+template <typename TH, typename TT, typename R>
 static void mt_bwd_launch(int64_t n, int64_t n_t, int F, const void* h, int64_t ld, const void* T,
                           int64_t t_ld, const float* coef, const float* gloss, float* dH,
-                          hipStream_t s) {
+                          hipStream_t s, R rows) {
   constexpr int V = MtGeo<TH, TT>::V;
   const int rows_per_block = kMtWaves * (kWave / (F / V)) * 4;
-  hipLaunchKernelGGL((mt_bwd_kernel<TH, TT>), dim3(grid_for(n, rows_per_block, 1 << 16)),
-                     dim3(kMtThreads), 0, s, n, n_t, F, (const TH*)h, ld, (const TT*)T, t_ld, coef,
-                     gloss, dH);
+  hipLaunchKernelGGL((mt_bwd_kernel<TH, TT, R>),
+                     dim3(grid_for(rows.grid_rows(n), rows_per_block, 1 << 16)), dim3(kMtThreads),
+                     0, s, n, n_t, F, (const TH*)h, ld, (const TT*)T, t_ld, coef, gloss, dH, rows);
 }
+
+// the rows that occur: count[r] > 0 (the forward's histogram, or its identity counts)
+struct MtCountFlag {
+  const int32_t* count;
+  __device__ __forceinline__ int operator()(int64_t r) const { return count[r] > 0 ? 1 : 0; }
+};
 
 // FN<student type, teacher type>(...) for the four dtype pairs
 #define MT_DISPATCH(FN, HD, TD, ...)                           \
@@ -512,6 +523,43 @@ extern "C" int msha_link_match_bwd(int32_t feat, int32_t h_dtype, const void* h,
   MSHA_ARG_CHECK(((uintptr_t)dH % 16) == 0, "link_match_bwd: dH must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   MT_DISPATCH(mt_bwd_launch, h_dtype, t_dtype, n, n_t, (int)feat, h, ld, teacher, t_ld, coef,
-              gloss, dH, s);
+              gloss, dH, s, PgAllRows{});
   return check_launch("link_match_bwd");
+}
+
+extern "C" int msha_link_match_rows(int64_t n_entries, int64_t n, const int32_t* count,
+                                    int32_t* rows, int32_t* n_rows, void* ws, size_t ws_bytes,
+                                    msha_stream_t stream) {
+  MSHA_ARG_CHECK(n_entries >= 1 && n_entries <= kMtMaxEntries,
+                 "link_match_rows: bad sizes (1 <= n_entries < 2^31)");
+  MSHA_ARG_CHECK(n >= 1 && n < kMtMaxRows, "link_match_rows: bad sizes (1 <= n < 2^31 - 1)");
+  MSHA_ARG_CHECK(count && rows && n_rows, "link_match_rows: null pointer");
+  MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= rl_layout(n).total && ((uintptr_t)ws % 16) == 0,
+                 "link_match_rows: workspace too small or unaligned "
+                 "(msha_plan_rows_workspace_size)");
+  const int64_t cap = n < n_entries ? n : n_entries;
+  rl_build(n, cap, MtCountFlag{count}, rows, n_rows, ws, (hipStream_t)stream);
+  return check_launch("link_match_rows");
+}
+
+extern "C" int msha_link_match_bwd_rows(int64_t n_entries, int32_t feat, int32_t h_dtype,
+                                        const void* h, int64_t ld, int64_t n, int32_t t_dtype,
+                                        const void* teacher, int64_t t_ld, int64_t n_t,
+                                        const float* coef, const float* gloss,
+                                        const int32_t* rows, const int32_t* n_rows, int64_t cap,
+                                        float* vals, msha_stream_t stream) {
+  MSHA_ARG_CHECK(n_entries >= 1 && n_entries <= kMtMaxEntries,
+                 "link_match_bwd_rows: bad sizes (1 <= n_entries < 2^31)");
+  const int rc = mt_tables_check("link_match_bwd_rows", feat, h_dtype, h, ld, n, t_dtype, teacher,
+                                 t_ld, n_t);
+  if (rc != MSHA_OK) return rc;
+  MSHA_ARG_CHECK(coef && gloss && rows && n_rows && vals, "link_match_bwd_rows: null pointer");
+  MSHA_ARG_CHECK(cap == (n < n_entries ? n : n_entries),
+                 "link_match_bwd_rows: cap must be min(n, n_entries) (msha_link_match_rows)");
+  MSHA_ARG_CHECK(((uintptr_t)coef % 8) == 0, "link_match_bwd_rows: coef must be 8-byte aligned");
+  MSHA_ARG_CHECK(((uintptr_t)vals % 16) == 0, "link_match_bwd_rows: vals must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  MT_DISPATCH(mt_bwd_launch, h_dtype, t_dtype, n, n_t, (int)feat, h, ld, teacher, t_ld, coef,
+              gloss, vals, s, PgListRows{rows, n_rows, cap});
+  return check_launch("link_match_bwd_rows");
 }

@@ -36,7 +36,10 @@
 // An entry whose source lies outside [0, n) is padding: its logp row is NaN and it adds to no
 // gradient.  A virtual (empty) row is skipped through rowflag: y = 0, logp =
 // log_softmax(relu(b2)), dx = 0.  Every index is range-checked before a load goes through it.
+#include <type_traits>
+
 #include "common.h"
+#include "pair_grad.h"
 
 namespace msha {
 
@@ -390,27 +393,33 @@ __global__ void __launch_bounds__(kSgThreads) sage_wfinish_kernel(
 
 // dS[r] = the dx rows of r's batch entries in batch order, a float4 a thread.  The plan is
 // that of the pair list (src, src): row r's range holds each entry b of r and b + B; the
-// second ends are skipped.  Every row is written.
+// second ends are skipped.  Every row is written.  R (pair_grad.h): every table row to dS[r]
+// (PgAllRows), or entry i of the plan's touched-row list to vals[i] (PgListRows: the loop runs
+// to the list's capacity; an entry past the device count or outside the table is exact zeros).
+template <typename R>
 __global__ void __launch_bounds__(kSgThreads) sage_table_kernel(
     int64_t B, int64_t n, int in, const int32_t* __restrict__ rowptr,
-    const int32_t* __restrict__ ent, const float* __restrict__ dx, float* __restrict__ dS) {
+    const int32_t* __restrict__ ent, const float* __restrict__ dx, float* __restrict__ dS,
+    R rows) {
   const int LPR = in / 4;
-  const int64_t total = n * LPR;
+  const int64_t cnt = rows.count(n), total = rows.extent(n) * LPR;
   for (int64_t t = (int64_t)blockIdx.x * kSgThreads + threadIdx.x; t < total;
        t += (int64_t)gridDim.x * kSgThreads) {
-    const int64_t r = t / LPR;
+    const int64_t i = t / LPR;
     const int c = 4 * (int)(t % LPR);
-    int64_t b = rowptr[r], e = rowptr[r + 1];
+    const int64_t r = rows.row(i, cnt);
+    int64_t b = 0, e = 0;
+    if ((uint64_t)r < (uint64_t)n) b = rowptr[r], e = rowptr[r + 1];
     if (b < 0 || e < b || e > 2 * B) b = e = 0;  // (not a plan of this list)
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t i = b; i < e; ++i) {
-      const int64_t p = ent[i];
+    for (int64_t k = b; k < e; ++k) {
+      const int64_t p = ent[k];
       if ((uint64_t)p < (uint64_t)B) {
         const float4 v = *reinterpret_cast<const float4*>(dx + p * in + c);
         s = make_float4(s.x + v.x, s.y + v.y, s.z + v.z, s.w + v.w);
       }
     }
-    *reinterpret_cast<float4*>(dS + r * in + c) = s;
+    *reinterpret_cast<float4*>(dS + i * in + c) = s;
   }
 }
 
@@ -433,7 +442,8 @@ static int64_t sg_wg_per(int64_t B) {
 static int sg_len(int32_t in, int32_t M, int32_t out) { return M * in + M + out * M + out; }
 
 struct SgLayout {
-  size_t dr, ez, ey, dx, part, prow, pent, ptab, pws, total;
+  size_t dr, ez, ey, dx, part, prow, pent, ptab, pws, total;  // msha_sage_workspace_size
+  size_t rws, rows_total;  // + msha_plan_rows' workspace: msha_sage_rows_workspace_size
 };
 static SgLayout sg_layout(int64_t B, int64_t n, int32_t in, int32_t M, int32_t out) {
   SgLayout L;
@@ -457,6 +467,8 @@ static SgLayout sg_layout(int64_t B, int64_t n, int32_t in, int32_t M, int32_t o
   L.pws = off;
   off += sg_align(msha_pair_plan_workspace_size(B) + 16);
   L.total = off;
+  L.rws = off;
+  L.rows_total = off + sg_align(msha_plan_rows_workspace_size(n));
   return L;
 }
 
@@ -519,23 +531,47 @@ extern "C" int msha_sage_fwd(const msha_graph* g, int64_t B, const int64_t* src,
   return check_launch("sage_fwd");
 }
 
-extern "C" int msha_sage_bwd(const msha_graph* g, int64_t B, const int64_t* src, int32_t in,
-                             int32_t out, const float* table, int64_t ld, const float* vals,
-                             const float* W1, const float* b1, const float* W2, const float* b2,
-                             const float* logp, const float* dlogp, float* dS, float* dW1,
-                             float* db1, float* dW2, float* db2, void* ws, size_t ws_bytes,
-                             msha_stream_t stream) {
-  const int rc = sg_check("sage_bwd", g, B, src, in, out, table, ld, vals, W1, b1, W2, b2);
+namespace msha {
+
+// where the table gradient goes: dS (n, in), every row; or the touched-row list of the batch
+// (rows, n_rows: written by the call) and its (cap, in) vals
+struct SgDense {
+  using Policy = PgAllRows;
+  static constexpr const char* kOutS = "dS";
+  Policy policy() const { return {}; }
+};
+struct SgList {
+  using Policy = PgListRows;
+  static constexpr const char* kOutS = "vals";
+  int32_t *list, *count_out;
+  int64_t cap;
+  Policy policy() const { return {list, count_out, cap}; }
+};
+
+// msha_sage_bwd (R = SgDense, dS = the (n, in) gradient, nullable) and msha_sage_bwd_rows (R =
+// SgList, dS = vals): one row pass, one weight gradient, one (src, src) plan
+template <typename R>
+static int sg_bwd_run(const char* name, const msha_graph* g, int64_t B, const int64_t* src,
+                      int32_t in, int32_t out, const float* table, int64_t ld, const float* vals,
+                      const float* W1, const float* b1, const float* W2, const float* b2,
+                      const float* logp, const float* dlogp, float* dS, float* dW1, float* db1,
+                      float* dW2, float* db2, void* ws, size_t ws_bytes, msha_stream_t stream,
+                      R rows) {
+  constexpr bool kList = std::is_same<R, SgList>::value;
+  const std::string nm(name);
+  const int rc = sg_check(name, g, B, src, in, out, table, ld, vals, W1, b1, W2, b2);
   if (rc != MSHA_OK) return rc;
-  MSHA_ARG_CHECK(B == 0 || (logp && dlogp), "sage_bwd: null pointer");
+  MSHA_ARG_CHECK(B == 0 || (logp && dlogp), nm + ": null pointer");
   MSHA_ARG_CHECK((dW1 != nullptr) == (db1 != nullptr) && (dW1 != nullptr) == (dW2 != nullptr) &&
                      (dW1 != nullptr) == (db2 != nullptr),
-                 "sage_bwd: dW1, db1, dW2 and db2 come together or not at all");
-  MSHA_ARG_CHECK(((uintptr_t)dS % 16) == 0, "sage_bwd: dS must be 16-byte aligned");
+                 nm + ": dW1, db1, dW2 and db2 come together or not at all");
+  MSHA_ARG_CHECK(((uintptr_t)dS % 16) == 0, nm + ": " + R::kOutS + " must be 16-byte aligned");
   const int M = (int)g->n_cols;
   const SgLayout L = sg_layout(B, g->n_rows, in, M, out);
-  MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= L.total && ((uintptr_t)ws % 16) == 0,
-                 "sage_bwd: workspace too small or unaligned (msha_sage_workspace_size)");
+  MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= (kList ? L.rows_total : L.total) &&
+                     ((uintptr_t)ws % 16) == 0,
+                 nm + ": workspace too small or unaligned (" +
+                     (kList ? "msha_sage_rows_workspace_size" : "msha_sage_workspace_size") + ")");
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)ws;
   float* dr = (float*)(w + L.dr);
@@ -557,16 +593,58 @@ extern "C" int msha_sage_bwd(const msha_graph* g, int64_t B, const int64_t* src,
                        s, nblk, len, M * in, M * in + M, M * in + M + out * M, part, dW1, db1, dW2,
                        db2);
   }
-  if (dS != nullptr) {
+  if (dS != nullptr || kList) {  // (a list of capacity 0 still gets its count)
     int32_t* prow = (int32_t*)(w + L.prow);
     int32_t* pent = (int32_t*)(w + L.pent);
     int32_t* ptab = (int32_t*)(w + L.ptab);
     const int prc = msha_pair_plan(B, g->n_rows, src, src, prow, pent, ptab, w + L.pws,
-                                   ws_bytes - L.pws, stream);
+                                   L.total - L.pws, stream);
     if (prc != MSHA_OK) return prc;
-    hipLaunchKernelGGL(sage_table_kernel,
-                       dim3(grid_for(g->n_rows * (in / 4), kSgThreads, 1 << 16)),
-                       dim3(kSgThreads), 0, s, B, g->n_rows, (int)in, prow, pent, dx, dS);
+    if constexpr (kList) {  // the touched rows of that plan: the distinct valid sources
+      const int lrc = msha_plan_rows(g->n_rows, B, prow, rows.list, rows.count_out, w + L.rws,
+                                     L.rows_total - L.rws, stream);
+      if (lrc != MSHA_OK) return lrc;
+    }
+    if (dS != nullptr)
+      hipLaunchKernelGGL((sage_table_kernel<typename R::Policy>),
+                         dim3(grid_for(rows.policy().grid_rows(g->n_rows) * (in / 4), kSgThreads,
+                                       1 << 16)),
+                         dim3(kSgThreads), 0, s, B, g->n_rows, (int)in, prow, pent, dx, dS,
+                         rows.policy());
   }
-  return check_launch("sage_bwd");
+  return check_launch(name);
+}
+
+}  // namespace msha
+
+extern "C" int msha_sage_bwd(const msha_graph* g, int64_t B, const int64_t* src, int32_t in,
+                             int32_t out, const float* table, int64_t ld, const float* vals,
+                             const float* W1, const float* b1, const float* W2, const float* b2,
+                             const float* logp, const float* dlogp, float* dS, float* dW1,
+                             float* db1, float* dW2, float* db2, void* ws, size_t ws_bytes,
+                             msha_stream_t stream) {
+  return sg_bwd_run("sage_bwd", g, B, src, in, out, table, ld, vals, W1, b1, W2, b2, logp, dlogp,
+                    dS, dW1, db1, dW2, db2, ws, ws_bytes, stream, SgDense{});
+}
+
+extern "C" size_t msha_sage_rows_workspace_size(int64_t B, int64_t n, int32_t in, int32_t M,
+                                                int32_t out) {
+  if (msha_sage_workspace_size(B, n, in, M, out) == 0 || n >= ((int64_t)1 << 31) - 1) return 0;
+  return sg_layout(B, n, in, M, out).rows_total;
+}
+
+extern "C" int msha_sage_bwd_rows(const msha_graph* g, int64_t B, const int64_t* src, int32_t in,
+                                  int32_t out, const float* table, int64_t ld, const float* vals,
+                                  const float* W1, const float* b1, const float* W2,
+                                  const float* b2, const float* logp, const float* dlogp,
+                                  float* dW1, float* db1, float* dW2, float* db2, int32_t* rows,
+                                  int32_t* n_rows, int64_t cap, float* row_vals, void* ws,
+                                  size_t ws_bytes, msha_stream_t stream) {
+  MSHA_ARG_CHECK(g != nullptr, "sage_bwd_rows: graph CSR or edge values missing");
+  MSHA_ARG_CHECK(n_rows && (cap == 0 || (rows && row_vals)), "sage_bwd_rows: null pointer");
+  MSHA_ARG_CHECK(B >= 0 && cap == pg_rows_cap(g->n_rows, B),
+                 "sage_bwd_rows: cap must be min(n, 2 * B) (the (src, src) plan's list)");
+  return sg_bwd_run("sage_bwd_rows", g, B, src, in, out, table, ld, vals, W1, b1, W2, b2, logp,
+                    dlogp, row_vals, dW1, db1, dW2, db2, ws, ws_bytes, stream,
+                    SgList{rows, n_rows, cap});
 }

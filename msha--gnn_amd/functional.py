@@ -845,6 +845,8 @@ class _Sage(torch.autograd.Function):
         W1, b1, W2, b2 = (t.detach().contiguous() for t in (W1, b1, W2, b2))
         logp = _sage_fwd(tb, src, graph, vals, W1, b1, W2, b2)
         ctx.graph = graph
+        # the registered table itself: the (src, src) plan's list has min(n, 2B) entries
+        ctx.leaf = _row_leaf(table, min(tb.shape[0], 2 * src.numel()))
         ctx.save_for_backward(tb, W1, b1, W2, b2, src, vals, logp)
         return logp
 
@@ -858,16 +860,26 @@ class _Sage(torch.autograd.Function):
         need_t, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:5])
         dl = dlogp.detach().to(torch.float32).contiguous()
         dS = dW1 = db1 = dW2 = db2 = None
-        if need_t:
-            dS = torch.empty(n, in_f, dtype=torch.float32, device=dev)
         if need_w:
             dW1, db1, dW2, db2 = (torch.empty_like(t) for t in (W1, b1, W2, b2))
-        ws = _workspace(dev, _lib.fn("msha_sage_workspace_size")(B, n, in_f, g.n_cols, out))
-        _lib.call("msha_sage_bwd", g.desc, B, src.data_ptr(), in_f, out, tb.data_ptr(),
-                  tb.stride(0), vals.data_ptr(), W1.data_ptr(), b1.data_ptr(), W2.data_ptr(),
-                  b2.data_ptr(), logp.data_ptr(), dl.data_ptr(), _lib.ptr(dS), _lib.ptr(dW1),
-                  _lib.ptr(db1), _lib.ptr(dW2), _lib.ptr(db2), ws.data_ptr(), ws.numel(),
-                  _stream(tb))
+        head = (g.desc, B, src.data_ptr(), in_f, out, tb.data_ptr(), tb.stride(0),
+                vals.data_ptr(), W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(),
+                logp.data_ptr(), dl.data_ptr())
+        wgrads = (_lib.ptr(dW1), _lib.ptr(db1), _lib.ptr(dW2), _lib.ptr(db2))
+        if need_t and ctx.leaf is not None:
+            # a fuse_row_grad table: the batch's rows and their gradient go to its optimizer
+            # (the call itself lists the rows of its (src, src) plan); no (n, in) buffer
+            ws = _workspace(dev, _lib.fn("msha_sage_rows_workspace_size")(B, n, in_f, g.n_cols,
+                                                                         out))
+            _stash_rows(ctx.leaf, min(n, 2 * B), lambda *rows_vals: _lib.call(
+                "msha_sage_bwd_rows", *head, *wgrads, *rows_vals, ws.data_ptr(), ws.numel(),
+                _stream(tb)))
+        else:
+            if need_t:
+                dS = torch.empty(n, in_f, dtype=torch.float32, device=dev)
+            ws = _workspace(dev, _lib.fn("msha_sage_workspace_size")(B, n, in_f, g.n_cols, out))
+            _lib.call("msha_sage_bwd", *head, _lib.ptr(dS), *wgrads, ws.data_ptr(), ws.numel(),
+                      _stream(tb))
         need = ctx.needs_input_grad
         return (dS, dW1 if need[1] else None, db1 if need[2] else None,
                 dW2 if need[3] else None, db2 if need[4] else None, None, None, None)
@@ -897,7 +909,11 @@ def sage_forward(table, src, graph, vals, W1, b1, W2, b2, check=True):
     The forward keeps only its output; the backward recomputes the entry.  No float atomics:
     the weight gradients are block partials added in a fixed order, the table gradient adds the
     entries of a row in batch order (exact zeros for rows outside the batch), so every
-    result is bitwise reproducible.  Nothing is read back with ``check=False``."""
+    result is bitwise reproducible.  Nothing is read back with ``check=False``.  When
+    ``table`` is itself a leaf registered with ``optim.Adam.fuse_row_grad``, its gradient is
+    formed on the batch's distinct sources only (``RowGrad``, the dense gradient's rows bit
+    for bit; the backward call lists them) and handed to that optimizer; ``table.grad`` stays
+    None."""
     for name, t in (("table", table), ("W1", W1), ("b1", b1), ("W2", W2), ("b2", b2),
                     ("vals", vals)):
         if t.dtype != torch.float32:
@@ -1667,8 +1683,10 @@ class RowGrad:
 
 def _row_leaf(h, plan):
     """``h`` itself when it is a leaf table registered with ``optim.Adam.fuse_row_grad`` that
-    needs a gradient (its backward then forms a ``RowGrad``), else None."""
-    if plan is None or not (h.requires_grad and h.is_leaf and h.is_contiguous()):
+    needs a gradient (its backward then forms a ``RowGrad``), else None.  ``plan``: the
+    PairPlan whose touched rows the gradient has, or the capacity of a row list that the
+    backward's own launches build (``_stash_rows``); None or 0: no row path."""
+    if not plan or not (h.requires_grad and h.is_leaf and h.is_contiguous()):
         return None
     from .optim import row_optimizer_of
 
@@ -1677,17 +1695,54 @@ def _row_leaf(h, plan):
 
 def _stash_rows(leaf, plan, launch):
     """Backward of a registered leaf: ``launch(rows, n_rows, cap, vals)`` fills the compact
-    gradient, which goes to the leaf's optimizer in place of ``.grad``."""
+    gradient, which goes to the leaf's optimizer in place of ``.grad``.  ``plan``: a PairPlan
+    (the list is its ``plan_rows``), or an int, the capacity of a list that ``launch`` itself
+    writes into ``rows`` and ``n_rows``."""
     from .optim import row_optimizer_of
 
     opt = row_optimizer_of(leaf)
     if opt is None:
         raise RuntimeError("msha: the optimizer of a fuse_row_grad table is gone before its "
                            "backward")
-    rows, n_rows = plan_rows(plan)
+    if isinstance(plan, PairPlan):
+        rows, n_rows = plan_rows(plan)
+    else:
+        rows = torch.empty(int(plan), dtype=torch.int32, device=leaf.device)
+        n_rows = torch.empty((), dtype=torch.int32, device=leaf.device)
     vals = torch.empty(rows.numel(), leaf.shape[1], dtype=torch.float32, device=leaf.device)
-    opt.stash_row_grad(leaf, RowGrad(rows, n_rows, vals, leaf.shape))  # raises on a second one
+    opt.stash_row_grad(leaf, RowGrad(rows, n_rows, vals, leaf.shape))  # raises past its limit
     launch(rows.data_ptr(), n_rows.data_ptr(), rows.numel(), vals.data_ptr())
+
+
+def row_grad_union(grads):
+    """The sum of 2 to 4 ``RowGrad``s of one table as one ``RowGrad`` (``msha_row_grad_union``):
+    ``rows`` the ascending union (capacity ``min(n, sum of the capacities)``), ``values[i]`` the
+    rows' values added left to right in fp32, +0.0 where a list does not hold the row -- what
+    accumulating the dense fp32 gradients in that order gives, bit for bit.  Nothing is read
+    back (capturable)."""
+    grads = list(grads)
+    if not 2 <= len(grads) <= _lib.MAX_ROW_LISTS:
+        raise ValueError(f"row_grad_union: takes 2 to {_lib.MAX_ROW_LISTS} row gradients, got "
+                         f"{len(grads)}")
+    shape = grads[0].shape
+    if any(g.shape != shape for g in grads):
+        raise ValueError("row_grad_union: the row gradients are not of one table")
+    n, Fd = shape
+    dev = grads[0].values.device
+    _lib.require_cuda(*(g.values for g in grads))
+    lists = (_lib.MshaRowList * len(grads))()
+    for d, g in zip(lists, grads):
+        d.rows, d.n_rows = g.rows.data_ptr(), g.n_rows.data_ptr()
+        d.cap, d.vals = g.rows.numel(), g.values.data_ptr()
+    cap = min(n, sum(g.rows.numel() for g in grads))
+    rows = torch.empty(cap, dtype=torch.int32, device=dev)
+    n_rows = torch.empty((), dtype=torch.int32, device=dev)
+    vals = torch.empty(cap, Fd, dtype=torch.float32, device=dev)
+    ws = _workspace(dev, _lib.fn("msha_row_grad_union_workspace_size")(n))
+    _lib.call("msha_row_grad_union", n, Fd, len(grads), ctypes.byref(lists), rows.data_ptr(),
+              n_rows.data_ptr(), cap, vals.data_ptr(), ws.data_ptr(), ws.numel(),
+              _lib.stream_handle(dev))
+    return RowGrad(rows, n_rows, vals, shape)
 
 
 def sample_negatives(graph, src, k: int = 1, n_cand: int | None = None, seed: int | None = None,
@@ -1906,6 +1961,7 @@ class _LinkMLP(torch.autograd.Function):
                   _stream(hh))
         ctx.plan, ctx.dt, ctx.cfg = plan, dt, (w_label, w_mse, p)
         ctx.wdt, ctx.bdt = W.dtype, b.dtype
+        ctx.leaf = _row_leaf(h, plan)  # the registered table itself (its optimizer updates it)
         ctx.save_for_backward(hh, Wk, src, dst, label, teacher, out, pv)
         ctx.mark_non_differentiable(out, terms, pv)
         return loss, out, terms, pv
@@ -1927,22 +1983,29 @@ class _LinkMLP(torch.autograd.Function):
                 raise RuntimeError("link_mlp_loss: the gradient to h needs a PairPlan (h did not "
                                    "require grad when the loss was taken)")
             dx = torch.empty(P, Fd, dtype=torch.float32, device=dev)  # the one (P, F) buffer
-            dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
             W32 = _f32c(Wk)
         if need_w:
             dW = torch.empty(N, Fd, dtype=torch.float32, device=dev)
             db = torch.empty(N, dtype=torch.float32, device=dev)
         ws = _workspace(dev, _lib.fn("msha_link_mlp_bwd_workspace_size")(P, Fd, N))
-        _lib.call("msha_link_mlp_bwd", P, Fd, N, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n,
-                  src.data_ptr(), dst.data_ptr(), _lib.ptr(label), _lib.ptr(W32),
-                  _lib.ptr(teacher), out.data_ptr(), pv.data_ptr(), w_label, w_mse, p,
-                  g.data_ptr(), _lib.ptr(plan.rowptr if need_h else None),
-                  _lib.ptr(plan.ent if need_h else None),
-                  _lib.ptr(plan.chunk_tab if need_h else None), dz.data_ptr(), _lib.ptr(dx),
-                  _lib.ptr(dW), _lib.ptr(db), _lib.ptr(dH), ws.data_ptr(), ws.numel(),
-                  _stream(hh))
-        if need_h:
-            dH = _table_grad(dH, ctx.dt)
+        args = (P, Fd, N, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n, src.data_ptr(),
+                dst.data_ptr(), _lib.ptr(label), _lib.ptr(W32), _lib.ptr(teacher),
+                out.data_ptr(), pv.data_ptr(), w_label, w_mse, p, g.data_ptr(),
+                _lib.ptr(plan.rowptr if need_h else None), _lib.ptr(plan.ent if need_h else None),
+                _lib.ptr(plan.chunk_tab if need_h else None), dz.data_ptr(), _lib.ptr(dx),
+                _lib.ptr(dW), _lib.ptr(db))
+        tail = (ws.data_ptr(), ws.numel(), _stream(hh))
+        if need_h and ctx.leaf is not None:
+            # a fuse_row_grad table: the touched rows' gradient goes to its optimizer, no
+            # (n, F) buffer is formed and .grad stays None
+            _stash_rows(ctx.leaf, plan, lambda *rows_vals: _lib.call(
+                "msha_link_mlp_bwd_rows", *args, *rows_vals, *tail))
+        else:
+            if need_h:
+                dH = torch.empty(n, Fd, dtype=torch.float32, device=dev)
+            _lib.call("msha_link_mlp_bwd", *args, _lib.ptr(dH), *tail)
+            if need_h:
+                dH = _table_grad(dH, ctx.dt)
         if need_w:
             dW = dW if ctx.wdt == torch.float32 else dW.to(ctx.wdt)
             db = db if ctx.bdt == torch.float32 else db.to(ctx.bdt)
@@ -1975,7 +2038,10 @@ def link_mlp_loss(h, src, dst, W, b, *, label=None, teacher_out=None, w_label=1.
     loader, and the table gradient is summed per row in the order of ``plan``
     (``pair_plan(src, dst, n)``, built here when None and ``h`` needs a gradient; reuse it
     for as long as the pair list is unchanged).  No float atomics: bitwise reproducible.
-    Nothing is read back, so plan + loss + backward can be captured into one HIP graph."""
+    Nothing is read back, so plan + loss + backward can be captured into one HIP graph.
+    When ``h`` is itself a leaf registered with ``optim.Adam.fuse_row_grad``, its gradient is
+    formed on the plan's touched rows only (``RowGrad``, the dense gradient's rows bit for bit)
+    and handed to that optimizer; ``h.grad`` stays None."""
     _check_table_dtype("link_mlp_loss", h)
     _check_table_shape("link_mlp_loss", h)
     _pair_lists(src, dst, "link_mlp_loss")
@@ -2223,19 +2289,35 @@ class _LinkMatch(torch.autograd.Function):
                   coef.data_ptr(), cos_rows.data_ptr(), count.data_ptr(), loss.data_ptr(),
                   npad.data_ptr(), ws.data_ptr(), ws.numel(), s)
         ctx.dt = dt
-        ctx.save_for_backward(hh, th, coef)
+        # the registered table itself: the rows that occur are listed from count in the
+        # backward (rows=None names every row: dense)
+        ctx.leaf = _row_leaf(h, min(n, P) if rows is not None else None)
+        ctx.entries = P
+        ctx.save_for_backward(hh, th, coef, count)
         ctx.mark_non_differentiable(cos_rows, count, npad)
         return loss, cos_rows, count, npad
 
     @staticmethod
     def backward(ctx, gloss, _gc=None, _gn=None, _gp=None):
-        hh, th, coef = ctx.saved_tensors
+        hh, th, coef, count = ctx.saved_tensors
         n, Fd = hh.shape
         g = gloss.detach().to(torch.float32).reshape(1).contiguous()
+        args = (Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n, _code(th.dtype),
+                th.data_ptr(), th.stride(0), th.shape[0], coef.data_ptr(), g.data_ptr())
+        if ctx.leaf is not None and ctx.needs_input_grad[0]:
+            # a fuse_row_grad table: the rows that occur and their gradient go to its optimizer
+            P, s = ctx.entries, _stream(hh)
+            ws = _workspace(hh.device, _lib.fn("msha_plan_rows_workspace_size")(n))
+
+            def launch(rows, n_rows, cap, vals):
+                _lib.call("msha_link_match_rows", P, n, count.data_ptr(), rows, n_rows,
+                          ws.data_ptr(), ws.numel(), s)
+                _lib.call("msha_link_match_bwd_rows", P, *args, rows, n_rows, cap, vals, s)
+
+            _stash_rows(ctx.leaf, min(n, P), launch)
+            return None, None, None
         dH = torch.empty(n, Fd, dtype=torch.float32, device=hh.device)
-        _lib.call("msha_link_match_bwd", Fd, _code(ctx.dt), hh.data_ptr(), hh.stride(0), n,
-                  _code(th.dtype), th.data_ptr(), th.stride(0), th.shape[0], coef.data_ptr(),
-                  g.data_ptr(), dH.data_ptr(), _stream(hh))
+        _lib.call("msha_link_match_bwd", *args, dH.data_ptr(), _stream(hh))
         return _table_grad(dH, ctx.dt), None, None
 
 
@@ -2259,7 +2341,10 @@ def link_match_loss(h, rows, teacher_table, *, return_rows=False):
     table rows that occur: loss, counts and gradient are a function of the *multiset* of
     ``rows`` (and the tables) alone -- bitwise reproducible and unchanged by any permutation
     of ``rows`` -- with no float atomics, nothing (P, F)-sized and nothing read back, so
-    loss + backward can be captured into one HIP graph."""
+    loss + backward can be captured into one HIP graph.  When ``h`` is itself a leaf
+    registered with ``optim.Adam.fuse_row_grad`` and ``rows`` is given, its gradient is formed
+    on the rows that occur only (``RowGrad``: the ascending rows with a count, at most
+    min(n, P)) and handed to that optimizer; ``h.grad`` stays None."""
     t = teacher_table
     _check_table_dtype("link_match_loss", h)
     _check_table_dtype("link_match_loss", t, "teacher table")

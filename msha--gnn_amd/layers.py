@@ -451,7 +451,10 @@ class LinkPredictor(torch.nn.Module):
         to ``dst`` as the reference uses it (``functional.link_mlp_loss``: deterministic
         gradients to ``h`` and to the first Linear).  The defaults are LLP.py's
         ``--True_label`` and ``--KD_p``.  'mlp' with one used Linear only (the reference's
-        ``num_layers = 2``): a deeper head is not covered by the fused loss."""
+        ``num_layers = 2``): a deeper head is not covered by the fused loss.  When ``h`` is
+        itself a table registered with ``optim.Adam.fuse_row_grad``, only the rows the pairs
+        touch get a gradient and an update; register with ``accumulate=True`` to add
+        ``match_loss`` on the same table in one step."""
         if self.predictor != "mlp":
             raise ValueError(f"LinkPredictor.llp_loss needs the 'mlp' predictor, got "
                              f"{self.predictor!r}: the 'inner' objective is LinkPredictor.loss / "
@@ -468,7 +471,9 @@ class LinkPredictor(torch.nn.Module):
         """LLP's representation-matching term ``KD_cosine(h[rows], teacher_h[rows])``
         (LLP.py:34-35, :237; ``functional.link_match_loss``: a histogram of ``rows`` and one
         pass over the rows that occur, with a deterministic gradient to ``h``).  It compares
-        node rows, not pair scores, so it is the same for every predictor string."""
+        node rows, not pair scores, so it is the same for every predictor string.  When
+        ``h`` is itself a table registered with ``optim.Adam.fuse_row_grad``, only the rows
+        that occur get a gradient and an update."""
         return MF.link_match_loss(h, rows, teacher_h)
 
 
@@ -762,7 +767,9 @@ class GraphSAGE(nn.Module):
     then ``linear1`` and ``linear2`` in the reference's init order.  ``forward(source_index,
     adj)`` takes the dense (N, M) adjacency, hidden_features == M (SGAE.py:54 multiplies
     elementwise), and runs ``functional.sage_forward`` on the adjacency's cached CSR and edge
-    values: one launch forward, no dense ``adj[source_index]``."""
+    values: one launch forward, no dense ``adj[source_index]``.  With ``Sfeatures``
+    registered by ``optim.Adam.fuse_row_grad`` (its group without weight decay), only the
+    batch's rows get a gradient and an update."""
 
     def __init__(self, in_features, hidden_features, out_features, gdp):
         super().__init__()

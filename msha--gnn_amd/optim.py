@@ -17,11 +17,14 @@ at ``step()``.  The parameter's ``.grad`` stays None.  (One backward per step fo
 parameter: a second backward before ``step()`` raises, as accumulation would need the
 gradient this path never forms.)
 
-``fuse_row_grad(param)``: an embedding-style table trained by ``functional.link_bce_loss`` /
-``link_distill_loss``.  Their backward hands this optimizer the gradient of the rows the
-batch touches (``functional.RowGrad``) instead of an (n, F) ``.grad``, and ``step()`` runs
+``fuse_row_grad(param)``: an embedding-style table trained by ``functional.link_bce_loss``,
+``link_distill_loss``, ``link_mlp_loss``, ``link_match_loss`` or ``sage_forward``.  Their
+backward hands this optimizer the gradient of the rows the batch touches
+(``functional.RowGrad``) instead of an (n, F) ``.grad``, and ``step()`` runs
 ``msha_adam_rows_step`` over those rows: the same update with one global step count, the
-other rows neither read nor written.  ``state_dict`` is unchanged.
+other rows neither read nor written.  With ``accumulate=True`` up to four such gradients of
+one table (LLP's label + matching + distillation terms) are summed before the step
+(``msha_row_grad_union``).  ``state_dict`` is unchanged.
 """
 from __future__ import annotations
 
@@ -33,6 +36,7 @@ import torch
 from . import _lib
 
 _DT = {torch.float32: 0, torch.bfloat16: 1}
+MAX_ROW_GRADS = _lib.MAX_ROW_LISTS  # pending row gradients of a fuse_row_grad(accumulate=True) table
 
 
 class Adam(torch.optim.Optimizer):
@@ -139,14 +143,14 @@ class Adam(torch.optim.Optimizer):
             for p in group["params"]:
                 if row_optimizer_of(p) is self:
                     self._check_row_group(group)
-                    rg = getattr(p, "_msha_row_grad", None)
+                    rg = self.row_grad_of(p)  # several pending: merged once
                     if rg is not None:  # the touched rows' gradient: a lazy step over them
                         if p.grad is not None:
                             raise RuntimeError(
                                 "msha Adam: a fuse_row_grad parameter has both a row gradient "
                                 "and a .grad (it has another consumer besides its link loss): "
                                 "do not register it")
-                        p._msha_row_grad = None
+                        _drop_row_grads(p)
                         self._rows_step(group, p, rg)
                         continue
                 stash = getattr(p, "_msha_dropout_grad", None)
@@ -179,8 +183,7 @@ class Adam(torch.optim.Optimizer):
             for p in group["params"]:
                 if getattr(p, "_msha_dropout_grad", None) is not None:
                     p._msha_dropout_grad = None
-                if getattr(p, "_msha_row_grad", None) is not None:
-                    p._msha_row_grad = None
+                _drop_row_grads(p)
 
     # ------------------------------------------------- row-sparse table updates
     @staticmethod
@@ -190,18 +193,23 @@ class Adam(torch.optim.Optimizer):
                              "parameter group (L2 decay makes the gradient dense; this "
                              "optimizer has no decoupled decay)")
 
-    def fuse_row_grad(self, param):
+    def fuse_row_grad(self, param, accumulate=False):
         """Train the 2-D leaf table ``param`` at the cost of the rows a batch touches;
-        returns ``param``.  ``functional.link_bce_loss`` / ``link_distill_loss`` called on
+        returns ``param``.  ``functional.link_bce_loss``, ``link_distill_loss``,
+        ``link_mlp_loss``, ``link_match_loss`` (with ``rows``) and ``sage_forward`` called on
         the table itself then hand their backward's ``functional.RowGrad`` (the touched rows
-        of the plan and their fp32 gradient rows, bit for bit the dense gradient's) to this
+        of the batch and their fp32 gradient rows, bit for bit the dense gradient's) to this
         optimizer in place of ``param.grad``, which stays None: no (n, F) gradient is
         allocated.  ``step()`` runs ``msha_adam_rows_step`` over those rows: this
         optimizer's update with one global step count, for the touched rows only; the
         moments of the other rows are not decayed (``torch.optim.SparseAdam``'s rule with
         eps inside the bias correction).  A step that touches every row leaves the bits of
         the unregistered update.  One row gradient per step (a second backward before
-        ``step()`` raises); the group's ``weight_decay`` must be 0.  A view, a cast or an
+        ``step()`` raises) unless ``accumulate`` is set: then up to four row gradients may
+        arrive before ``step()`` (several losses on one table, or one backward of their sum),
+        and ``step()`` first sums them in arrival order over the union of their rows
+        (``functional.row_grad_union``: for fp32 the bits of accumulating the dense gradients).
+        The group's ``weight_decay`` must be 0.  A view, a cast or an
         encoder's output of the table takes the dense path as before.  When a batch names
         every row (P in the millions on a 100k-row table) the list adds work and nothing is
         saved: the registered step may then be slower than the dense one
@@ -212,22 +220,39 @@ class Adam(torch.optim.Optimizer):
                              f"{tuple(param.shape)}")
         self._check_row_group(group)
         param._msha_row_adam = weakref.ref(self)
+        param._msha_row_accumulate = bool(accumulate)
         return param
 
     def stash_row_grad(self, param, row_grad):
-        """Called from a link loss's backward: keep the table's ``functional.RowGrad`` for
+        """Called from a loss's backward: keep the table's ``functional.RowGrad`` for
         ``step()`` in place of ``param.grad``."""
-        if getattr(param, "_msha_row_grad", None) is not None:
+        pending = getattr(param, "_msha_row_grads", None) or []
+        if pending and not getattr(param, "_msha_row_accumulate", False):
             raise RuntimeError("msha Adam: a fuse_row_grad table got a second backward before "
                                "step(); one row gradient per step (do not register a table "
-                               "that two losses share)")
+                               "that two losses share, or register it with accumulate=True)")
+        if len(pending) >= MAX_ROW_GRADS:
+            raise RuntimeError(f"msha Adam: a fuse_row_grad(accumulate=True) table takes at most "
+                               f"{MAX_ROW_GRADS} row gradients per step")
         if tuple(row_grad.shape) != tuple(param.shape):
             raise ValueError("msha Adam: the row gradient is not of this table's shape")
-        param._msha_row_grad = row_grad
+        param._msha_row_grads = pending + [row_grad]
+        param._msha_row_merged = None
 
     def row_grad_of(self, param):
-        """The pending ``functional.RowGrad`` of a registered table, or None."""
-        return getattr(param, "_msha_row_grad", None)
+        """The pending ``functional.RowGrad`` of a registered table, or None; with several
+        pending (``accumulate=True``) their sum, formed once and kept until ``step()`` or
+        ``zero_grad()``."""
+        pending = getattr(param, "_msha_row_grads", None)
+        if not pending:
+            return None
+        if len(pending) == 1:
+            return pending[0]
+        if getattr(param, "_msha_row_merged", None) is None:
+            from .functional import row_grad_union
+
+            param._msha_row_merged = row_grad_union(pending)
+        return param._msha_row_merged
 
     def _rows_step(self, group, p, rg):
         _lib.require_cuda(p, rg.values)
@@ -259,6 +284,12 @@ class Adam(torch.optim.Optimizer):
         dout = dout.contiguous()
         self._check(param, dout)
         param._msha_dropout_grad = (dout, float(p), int(seed))
+
+
+def _drop_row_grads(param):
+    if getattr(param, "_msha_row_grads", None):
+        param._msha_row_grads = None
+        param._msha_row_merged = None
 
 
 def row_optimizer_of(param):
