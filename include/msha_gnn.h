@@ -408,6 +408,48 @@ MSHA_API int32_t msha_gemm_bf16_loader(int64_t M, int64_t N, int64_t K, const vo
                                        int64_t sAm, int64_t sAk, const void* B, int64_t sBk,
                                        int64_t sBn);
 
+/* host-only (ABI 16, added): which kernel family a call with these arguments runs -- the
+ * answer of the predicates the launches themselves ask; nothing is launched and no pointer
+ * is dereferenced (only its alignment and NULL-ness enter).
+ *   MSHA_ROUTE_TILED     the tiled GEMM (gemm.hip / gemm_bf16.hip)
+ *   MSHA_ROUTE_RESIDENT  a resident-W kernel on the operands' own type (exact-fp32 MFMA or bf16)
+ *   MSHA_ROUTE_SPLIT     a resident-W kernel on split-bf16 products of fp32 operands
+ * The resident kernels take K and heads*feat (N) in {64, 128}, at least 1,024 rows, 16-byte
+ * aligned X / W / h (G / G2 / W / out), and row byte counts below 2^31.  The environment
+ * knob MSHA_SKINNY=0 sends every call to the tiled kernels.
+ * msha_project_scores_route (dtype MSHA_DTYPE_F32 / _BF16; al, ar as the call's; h the output):
+ *   with a score vector feat must be 16, 32, 64 or heads*feat (bf16: feat 8 is tiled; fp32:
+ *   feat 4 and 8 are tiled); fp32 from MSHA_PROJ_SPLIT_MIN_ROWS (65,536) rows is _SPLIT.
+ *   sched (nullable, 3 ints): waves per block, column parts per tail tile and staged columns
+ *   per pass of the chosen instance (0 0 0 when tiled).
+ * msha_pair_linear_route: both gathers given (gi, gj), ldg / ldg2 multiples of 4; _SPLIT is
+ *   the windowed gather (known g_rows / g2_rows, tables within 4 GiB less 512 bytes, n_pairs * N * 4 < 2^31),
+ *   _RESIDENT the plain one.  msha_pair_linear_bf16_route: ldg / ldg2 multiples of 8.
+ * msha_gemm_f32_head_outer_route: _RESIDENT where msha_gemm_f32_head_outer with operand 0
+ *   computes dX = (dh + de (x) a [+ de2 (x) a2]) W^T on the resident-W kernel: beta 0, A
+ *   (M x K) and C dense row-major, B given as W (N x K) row-major, feat >= 16. */
+#define MSHA_ROUTE_TILED 0
+#define MSHA_ROUTE_RESIDENT 1
+#define MSHA_ROUTE_SPLIT 2
+MSHA_API int32_t msha_project_scores_route(int64_t M, int64_t K, int32_t heads, int32_t feat,
+                                           int32_t dtype, const void* X, const void* W,
+                                           const float* al, const float* ar, const void* h,
+                                           int32_t* sched);
+MSHA_API int32_t msha_pair_linear_route(int64_t n_pairs, int64_t K, int64_t N, const float* G,
+                                        int64_t ldg, const int64_t* gi, const float* G2,
+                                        int64_t ldg2, const int64_t* gj, int64_t g_rows,
+                                        int64_t g2_rows, const float* W, const float* out);
+MSHA_API int32_t msha_pair_linear_bf16_route(int64_t n_pairs, int64_t K, int64_t N, const void* G,
+                                             int64_t ldg, const int64_t* gi, const void* G2,
+                                             int64_t ldg2, const int64_t* gj, const void* W,
+                                             const void* out);
+MSHA_API int32_t msha_gemm_f32_head_outer_route(int64_t M, int64_t N, int64_t K, const float* A,
+                                                int64_t sAm, int64_t sAk, const float* B,
+                                                int64_t sBk, int64_t sBn, const float* C,
+                                                int64_t ldc, float beta, int32_t operand,
+                                                int32_t heads, int32_t feat, const float* de,
+                                                const float* a, const float* a2);
+
 /* msha_gemm_f32 with the backward of msha_project_scores folded into one operand's
  * loads: operand 0 (A, M x K, K = heads*feat, sAk = 1) or 1 (B, K x N, N = heads*feat,
  * sBn = 1) is read as X + de (x) a [+ de2 (x) a2], i.e. X[r, c] + de[r, c/feat] a[c].
@@ -554,7 +596,7 @@ MSHA_API int msha_bn_lrelu_bwd(int64_t rows, int32_t channels, int32_t dtype, co
  * with G2 == NULL and gj == NULL the input is x_i alone (deeper predictor layers);
  * act bits: 1 bias, 2 relu, 4 dropout(drop_p, seed, offset), 8 sigmoid.
  * g_rows / g2_rows: the row counts of G / G2 (every gi / gj index below them; 0 =
- * unknown).  Known counts whose tables fit 4 GiB select the gather kernel with 32-bit
+ * unknown).  Known counts whose tables fit 4 GiB (less 512 bytes) select the gather kernel with 32-bit
  * buffer offsets (an index outside [0, rows) then reads zeros: negative indices are not
  * wrapped as torch indexing would wrap them, so callers pass valid indices). */
 MSHA_API int msha_pair_linear(int64_t n_pairs, int64_t K, int64_t N, const float* G, int64_t ldg,

@@ -17,6 +17,8 @@ ABI_VERSION = 16  # MSHA_ABI_VERSION of include/msha_gnn.h
 MSHA_OK, MSHA_ERR_ARG, MSHA_ERR_UNSUPPORTED, MSHA_ERR_HIP = 0, -1, -2, -3
 # MSHA_GEMM_LOADER_* (msha_gemm_f32_loader / msha_gemm_bf16_loader)
 GEMM_LOADER_SCALAR, GEMM_LOADER_BNF, GEMM_LOADER_AK, GEMM_LOADER_VEC = 0, 1, 2, 4
+# MSHA_ROUTE_* (msha_project_scores_route, msha_pair_linear(_bf16)_route, ..._head_outer_route)
+ROUTE_TILED, ROUTE_RESIDENT, ROUTE_SPLIT = 0, 1, 2
 
 
 class MshaLibraryError(RuntimeError):
@@ -227,6 +229,12 @@ SIGNATURES = {
     # operand-staging queries of the tiled GEMMs, host-only (ABI 16, added)
     "msha_gemm_f32_loader": (I32, [I64, I64, I64, P, I64, I64, P, I64, I64]),
     "msha_gemm_bf16_loader": (I32, [I64, I64, I64, P, I64, I64, P, I64, I64]),
+    # route queries of the resident-W kernels, host-only (ABI 16, added): MSHA_ROUTE_*
+    "msha_project_scores_route": (I32, [I64, I64, I32, I32, I32, P, P, P, P, P, P]),
+    "msha_pair_linear_route": (I32, [I64, I64, I64, P, I64, P, P, I64, P, I64, I64, P, P]),
+    "msha_pair_linear_bf16_route": (I32, [I64, I64, I64, P, I64, P, P, I64, P, P, P]),
+    "msha_gemm_f32_head_outer_route": (I32, [I64, I64, I64, P, I64, I64, P, I64, I64, P, I64, F32,
+                                             I32, I32, I32, P, P, P]),
     # device-side evaluation (ABI 16, added)
     "msha_eval_rows": (C.c_int, [I64, I32, I64, I32, P, I64, P, P, I64, P, P, P, P, P, P, P]),
     "msha_eval_loss": (C.c_int, [I64, I64, P, P, P]),

@@ -360,6 +360,9 @@ int skinny_pair_linear_bf16(int64_t P, int64_t K, int64_t N, const void* G, int6
 int skinny_dx(int64_t M, int64_t N, int64_t K, const float* Dh, const float* W, float* C,
               int hH, int hF, const float* d1, const float* a1, const float* d2, const float* a2,
               hipStream_t s);
+// skinny_dx's own coverage decision, nothing launched (skinny_route.h: 0 tiled, 1 resident)
+int skinny_dx_route(int64_t M, int64_t N, int64_t K, const void* Dh, const void* W, const void* C,
+                    int hH, int hF, const void* d1, const void* a1);
 // cs_tab (optional): also cs_out1[n] = sum_r de[r, n / hF] cs_tab[r, n] (cs_out2 with de2)
 // through the per-block partials in cs_part (2 x N x 256 floats); cs_tab has B's row pitch.
 // cs_w (optional, instead of cs_tab, where cs_tab = A^T-rows x cs_w): the same sums as

@@ -700,13 +700,26 @@ static void launch_ho(const GemmArgs& p, int splits, hipStream_t s) {
   }
 }
 
+// dX = (dh + de (x) a) W^T with W^T given as W (N, K) row-major and a dense C: the layout
+// the resident-W dx_kernel takes (gemm_run and msha_gemm_f32_head_outer_route ask this)
+static bool dx_layout(const GemmArgs& p, int ho, float beta) {
+  return ho == HO_A && beta == 0.f && p.sAk == 1 && p.sAm == p.K && p.sBk == 1 && p.sBn == p.K &&
+         p.ldc == p.N;
+}
+
+// msha_gemm_f32_head_outer's refusal (MSHA_ERR_UNSUPPORTED: the caller materialises the sum)
+static bool ho_fused_ok(const GemmArgs& p, int operand) {
+  const bool lay = operand == 0 ? p.sAk == 1 : p.sBn == 1;
+  const bool al = aligned16(p.ha) && (p.ha2 == nullptr || aligned16(p.ha2));
+  return lay && al && loader_of<A_STRIDED>(p) != MSHA_GEMM_LOADER_SCALAR;
+}
+
 // shared body of msha_gemm_f32 / msha_gemm_f32_head_outer
 static int gemm_run(GemmArgs& p, int ho, float beta, int32_t splits, void* ws, size_t ws_bytes,
                     hipStream_t s) {
   const int64_t M = p.M, N = p.N, K = p.K;
   // dX = (dh + de (x) a) W^T with W^T given as W (N, K) row-major: resident-W kernel
-  if (ho == HO_A && beta == 0.f && p.sAk == 1 && p.sAm == K && p.sBk == 1 && p.sBn == K &&
-      p.ldc == N &&
+  if (dx_layout(p, ho, beta) &&
       skinny_dx(M, N, K, p.A, p.B, p.C, p.hH, p.hF, p.de, p.ha, p.de2, p.ha2, s))
     return check_launch("gemm_f32");
   if (ho != HO_A && p.slab == nullptr &&
@@ -785,12 +798,28 @@ extern "C" int msha_gemm_f32_head_outer(int64_t M, int64_t N, int64_t K, const f
   p.B = B; p.sBk = sBk; p.sBn = sBn;
   p.C = C; p.ldc = ldc;
   p.de = de; p.ha = a; p.de2 = de2; p.ha2 = a2; p.hH = heads; p.hF = feat;
-  const bool lay = operand == 0 ? sAk == 1 : sBn == 1;
-  const bool al = aligned16(a) && (a2 == nullptr || aligned16(a2));
-  if (!lay || !al || loader_of<A_STRIDED>(p) == MSHA_GEMM_LOADER_SCALAR)
+  if (!ho_fused_ok(p, operand))
     return fail(MSHA_ERR_UNSUPPORTED, "gemm_f32_head_outer: the updated operand needs unit stride "
                                       "along heads*feat and 16-byte aligned, vectorizable operands");
   return gemm_run(p, operand == 0 ? HO_A : HO_B, beta, splits, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// host-only (ABI 16, added): 1 where msha_gemm_f32_head_outer with these arguments runs the
+// resident-W dx_kernel (skinny.hip), 0 where it runs the tiled kernel or refuses
+extern "C" int32_t msha_gemm_f32_head_outer_route(int64_t M, int64_t N, int64_t K, const float* A,
+                                                  int64_t sAm, int64_t sAk, const float* B,
+                                                  int64_t sBk, int64_t sBn, const float* C,
+                                                  int64_t ldc, float beta, int32_t operand,
+                                                  int32_t heads, int32_t feat, const float* de,
+                                                  const float* a, const float* a2) {
+  if (M <= 0 || N <= 0 || K <= 0 || heads <= 0 || feat <= 0 || (operand != 0 && operand != 1)) return 0;
+  GemmArgs p = base_args(M, N, K);
+  p.A = A; p.sAm = sAm; p.sAk = sAk;
+  p.B = B; p.sBk = sBk; p.sBn = sBn;
+  p.C = const_cast<float*>(C); p.ldc = ldc;
+  p.de = de; p.ha = a; p.ha2 = a2; p.hH = heads; p.hF = feat;
+  if (!ho_fused_ok(p, operand) || !dx_layout(p, operand == 0 ? HO_A : HO_B, beta)) return 0;
+  return skinny_dx_route(M, N, K, A, B, C, heads, feat, de, a);
 }
 
 extern "C" size_t msha_head_outer_colsum_workspace_size(int64_t N) {

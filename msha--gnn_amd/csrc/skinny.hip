@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "skinny_route.h"
 
 namespace msha {
 namespace sk {
@@ -732,7 +733,7 @@ __global__ void __launch_bounds__(64 * kProjWaves) pair_kernel(
 
 // ------------------------------------------- fp32 pair scorer on split bf16 MFMA ---
 // The fp32 pair scorer for tables inside a buffer window (msha_pair_linear's table_rows:
-// rows x ldg x 4 < 4 GiB; everything else takes pair_kernel).  The fp32 products are
+// rows x ldg x 4 <= 4 GiB - 512; everything else takes pair_kernel).  The fp32 products are
 // computed on the bf16 matrix pipe (16x the fp32 MFMA rate): every fp32 operand is split
 // into three bf16 terms, x = x_h + x_m + x_l (x_h = bf16(x), x_m = bf16(x - x_h), x_l =
 // bf16(x - x_h - x_m); both subtractions exact in fp32, |x - sum| <= 2^-27 |x|), and each
@@ -839,13 +840,19 @@ __global__ void __launch_bounds__(256 * WPS) pair_x3_kernel(
   // table; the test also keeps the index's high word live, so the register allocator does
   // not put the offset into the dead high half of the NEXT index load's destination (a
   // write that would wait on that load: vmcnt(0) at every tile start)
+  // (the masked offset stays past the window with every slot offset added: 0xFFFFFFF0 plus a
+  // slot's 16 .. 400 bytes wrapped past 2^32 into row 0 of the table, so an out-of-range
+  // index read zeros in slot 0 only; the host keeps the windows below route::kWindowMax)
+  constexpr uint32_t kPast = (uint32_t)route::kWindowMax;
+  static_assert(128u * (Gx::S - 1) + 16u + 16u <= 0x100000000ull - route::kWindowMax,
+                "a masked row's last slot must not wrap");
   const uint64_t rows_a = ((uint64_t)bytes_a - 4 * K) / (4 * (uint64_t)ldg) + 1;
   const uint64_t rows_b = ((uint64_t)bytes_b - 4 * K) / (4 * (uint64_t)ldg2) + 1;
   auto offset_a = [&](int64_t a) -> uint32_t {
-    return (uint64_t)a >= rows_a ? 0xFFFFFFF0u : (uint32_t)((a * ldg + 8 * g) * 4);
+    return (uint64_t)a >= rows_a ? kPast : (uint32_t)((a * ldg + 8 * g) * 4);
   };
   auto offset_b = [&](int64_t b) -> uint32_t {
-    return (uint64_t)b >= rows_b ? 0xFFFFFFF0u : (uint32_t)((b * ldg2 + 8 * g) * 4);
+    return (uint64_t)b >= rows_b ? kPast : (uint32_t)((b * ldg2 + 8 * g) * 4);
   };
   // slot 2 s + j: step s's columns [32 s + 8 g + 4 j, +4) at byte 128 s + 16 j
   auto slot_off = [](int i) -> uint32_t { return 128u * (i >> 1) + 16u * (i & 1); };
@@ -1888,17 +1895,19 @@ static int proj_grid(int64_t M, int waves = sk::kProjWaves) {
   return (int)(blocks < 256 ? blocks : 256);  // one 8-wave block per CU
 }
 
-// Returns 1 when it launched, 0 when the shape is not covered (caller falls back).
+static int64_t proj_split_min() {
+  static const int64_t rows = env_int("MSHA_PROJ_SPLIT_MIN_ROWS", 65536);
+  return rows;
+}
+
+// The projection's route (skinny_route.h: 0 tiled, 1 resident, 2 resident split-bf16) and,
+// with `launch`, the launch itself: one instance table for the launch and the host-only
+// query (msha_project_scores_route).  sched (nullable): WAVES, PT, SW of the instance's
+// ProjStage.
 template <typename T>
-int skinny_project(int64_t M, int64_t K, int heads, int feat, const void* X, const void* W,
-                   const float* al, const float* ar, void* h, float* el, float* er,
-                   hipStream_t s) {
-  const int64_t N = (int64_t)heads * feat;
-  if (!skinny_enabled() || M < 1024 || M * K * (int64_t)sizeof(T) >= (1ll << 31)) return 0;
-  if (((uintptr_t)X | (uintptr_t)W | (uintptr_t)h) & 15) return 0;
-  const bool score = al != nullptr || ar != nullptr;
-  const int minfe = 16 / (int)sizeof(T);
-  if (score && (feat < minfe || N % feat != 0)) return 0;
+static int project_go(bool launch, int32_t* sched, int64_t M, int64_t K, int heads, int feat,
+                      const void* X, const void* W, const float* al, const float* ar, void* h,
+                      float* el, float* er, hipStream_t s) {
   // fp32: the split-bf16 form from 64k rows (MSHA_PROJ_SPLIT_MIN_ROWS moves the cut-over
   // for A/B runs), the exact-fp32 MFMA below.  Kernel times with the column-wise W fill,
   // split vs exact fp32, 8 x 16 / 2 x 64: 100k rows 27 vs 35 / 25 vs 38 us, 65,536 19 vs 25 /
@@ -1908,21 +1917,34 @@ int skinny_project(int64_t M, int64_t K, int heads, int feat, const void* X, con
   // layer's input-gradient check on that graph then misses its bound in 1 of 6.4M
   // elements (1.07 x)
   constexpr bool kF32 = std::is_same<T, float>::value;
-  static const int64_t split_min = env_int("MSHA_PROJ_SPLIT_MIN_ROWS", 65536);
-  const bool split = kF32 && M >= split_min;
+  const route::Proj r =
+      route::project(skinny_enabled(), proj_split_min(), M, K, heads, feat, (int)sizeof(T),
+                     (uintptr_t)X, (uintptr_t)W, (uintptr_t)h, al != nullptr || ar != nullptr);
+  if (r.code == route::kTiled) return route::kTiled;
+  const int inst_fe = r.fe;
+  auto note = [&](int waves, int pt, int sw) {
+    if (sched != nullptr) { sched[0] = waves; sched[1] = pt; sched[2] = sw; }
+  };
 #define SKP(k, n, fe)                                                                           \
-  if (K == k && N == n && (score ? feat == fe : fe == 0)) {                                    \
-    if (split) {                                                                                \
-      constexpr int wv = sk::ProjStage<T, k, n, fe, kF32>::WAVES;                               \
-      hipLaunchKernelGGL((sk::proj_kernel<T, k, n, fe, kF32>), dim3(proj_grid(M, wv)),         \
+  if (r.K == k && r.N == n && inst_fe == fe) {                                                  \
+    if (r.code == route::kSplit) {                                                              \
+      using St = sk::ProjStage<T, k, n, fe, kF32>;                                              \
+      constexpr int wv = St::WAVES;                                                             \
+      note(wv, St::PT, St::SW);                                                                 \
+      if (launch)                                                                               \
+        hipLaunchKernelGGL((sk::proj_kernel<T, k, n, fe, kF32>), dim3(proj_grid(M, wv)),       \
+                           dim3(64 * wv), 0, s, (int)M, (const T*)X, (const T*)W, al, ar,       \
+                           (T*)h, el, er, heads);                                               \
+      return route::kSplit;                                                                     \
+    }                                                                                           \
+    using St = sk::ProjStage<T, k, n, fe, false>;                                               \
+    constexpr int wv = St::WAVES;                                                               \
+    note(wv, St::PT, St::SW);                                                                   \
+    if (launch)                                                                                 \
+      hipLaunchKernelGGL((sk::proj_kernel<T, k, n, fe, false>), dim3(proj_grid(M, wv)),        \
                          dim3(64 * wv), 0, s, (int)M, (const T*)X, (const T*)W, al, ar, (T*)h,  \
                          el, er, heads);                                                        \
-      return 1;                                                                                 \
-    }                                                                                           \
-    constexpr int wv = sk::ProjStage<T, k, n, fe, false>::WAVES;                                \
-    hipLaunchKernelGGL((sk::proj_kernel<T, k, n, fe, false>), dim3(proj_grid(M, wv)), dim3(64 * wv), \
-                       0, s, (int)M, (const T*)X, (const T*)W, al, ar, (T*)h, el, er, heads);   \
-    return 1;                                                                                   \
+    return route::kResident;                                                                    \
   }
 #define SKP_N(k, n) SKP(k, n, 0) SKP(k, n, 16) SKP(k, n, 32) SKP(k, n, 64) SKP(k, n, n)
   SKP_N(128, 128)
@@ -1931,7 +1953,15 @@ int skinny_project(int64_t M, int64_t K, int heads, int feat, const void* X, con
   SKP(64, 64, 0) SKP(64, 64, 16) SKP(64, 64, 32) SKP(64, 64, 64)
 #undef SKP_N
 #undef SKP
-  return 0;
+  return route::kTiled;
+}
+
+// Returns nonzero when it launched, 0 when the shape is not covered (caller falls back).
+template <typename T>
+int skinny_project(int64_t M, int64_t K, int heads, int feat, const void* X, const void* W,
+                   const float* al, const float* ar, void* h, float* el, float* er,
+                   hipStream_t s) {
+  return project_go<T>(true, nullptr, M, K, heads, feat, X, W, al, ar, h, el, er, s);
 }
 template int skinny_project<float>(int64_t, int64_t, int, int, const void*, const void*,
                                    const float*, const float*, void*, float*, float*, hipStream_t);
@@ -1940,20 +1970,27 @@ template int skinny_project<bf16_t>(int64_t, int64_t, int, int, const void*, con
 
 // pair linear on the resident-W kernels: fp32, both gathers given, K and N in {64, 128},
 // 16-byte aligned rows; 0 = not covered (the caller runs the tiled GEMM).  Tables with
-// known row counts inside a 4 GiB buffer window take pair_x3_kernel, the rest pair_kernel.
+// known row counts inside the buffer window (route::kWindowMax bytes) take pair_x3_kernel, the
+// rest pair_kernel.
+route::Pair skinny_pair_linear_route(int64_t P, int64_t K, int64_t N, const void* G, int64_t ldg,
+                                     const int64_t* gi, const void* G2, int64_t ldg2,
+                                     const int64_t* gj, int64_t g_rows, int64_t g2_rows,
+                                     const void* W, const void* out) {
+  return route::pair_linear(skinny_enabled(), P, K, N, (uintptr_t)G, ldg, gi != nullptr,
+                            (uintptr_t)G2, ldg2, gj != nullptr, g_rows, g2_rows, (uintptr_t)W,
+                            (uintptr_t)out);
+}
+
 int skinny_pair_linear(int64_t P, int64_t K, int64_t N, const float* G, int64_t ldg,
                        const int64_t* gi, const float* G2, int64_t ldg2, const int64_t* gj,
                        int64_t g_rows, int64_t g2_rows, const float* W, const float* bias,
                        int act, const Dropout& dp, float* out, hipStream_t s) {
-  if (!skinny_enabled() || P < 1024 || P >= (1ll << 31) || gi == nullptr || gj == nullptr) return 0;
-  if (G2 == nullptr) { G2 = G; ldg2 = ldg; g2_rows = g_rows; }
-  if (ldg % 4 || ldg2 % 4 || (((uintptr_t)G | (uintptr_t)G2 | (uintptr_t)out | (uintptr_t)W) & 15))
-    return 0;
-  // table bytes up to the last row's K columns (the kernel reads no further)
-  auto span = [&](int64_t rows, int64_t ld) -> int64_t { return rows > 0 ? ((rows - 1) * ld + K) * 4 : -1; };
-  const int64_t ba = span(g_rows, ldg), bb = span(g2_rows, ldg2);
-  const bool window = ba > 0 && bb > 0 && ba <= 0xFFFFFFFFll && bb <= 0xFFFFFFFFll &&
-                      P * N * 4 < (1ll << 31);
+  const route::Pair r = skinny_pair_linear_route(P, K, N, G, ldg, gi, G2, ldg2, gj, g_rows, g2_rows,
+                                                 W, out);
+  if (r.code == route::kTiled) return route::kTiled;
+  if (G2 == nullptr) { G2 = G; ldg2 = ldg; }
+  const bool window = r.code == route::kSplit;
+  const uint32_t ba = r.ba, bb = r.bb;
   const dim3 grid(proj_grid(P)), block(64 * sk::kProjWaves);
   constexpr int xw = 4 * PAIR_X3_WPS;
   const dim3 xgrid(proj_grid(P, xw)), xblock(64 * xw);
@@ -1961,26 +1998,31 @@ int skinny_pair_linear(int64_t P, int64_t K, int64_t N, const float* G, int64_t 
   if (K == k && N == n) {                                                                       \
     if (window)                                                                                 \
       hipLaunchKernelGGL((sk::pair_x3_kernel<k, n, PAIR_X3_WPS>), xgrid, xblock, 0, s, (int)P,  \
-                         G, ldg, gi, G2, ldg2, gj, W, bias, act, dp, out, (uint32_t)ba,         \
-                         (uint32_t)bb);                                                         \
+                         G, ldg, gi, G2, ldg2, gj, W, bias, act, dp, out, ba, bb);              \
     else                                                                                        \
       hipLaunchKernelGGL((sk::pair_kernel<k, n>), grid, block, 0, s, (int)P, G, ldg, gi, G2,   \
                          ldg2, gj, W, bias, act, dp, out);                                      \
-    return 1;                                                                                   \
+    return r.code;                                                                              \
   }
   SKPL(128, 128) SKPL(64, 128) SKPL(128, 64) SKPL(64, 64)
 #undef SKPL
   return 0;
 }
 
+int skinny_pair_linear_bf16_route(int64_t P, int64_t K, int64_t N, const void* G, int64_t ldg,
+                                  const int64_t* gi, const void* G2, int64_t ldg2,
+                                  const int64_t* gj, const void* W, const void* out) {
+  return route::pair_linear_bf16(skinny_enabled(), P, K, N, (uintptr_t)G, ldg, gi != nullptr,
+                                 (uintptr_t)G2, ldg2, gj != nullptr, (uintptr_t)W, (uintptr_t)out);
+}
+
 int skinny_pair_linear_bf16(int64_t P, int64_t K, int64_t N, const void* G, int64_t ldg,
                             const int64_t* gi, const void* G2, int64_t ldg2, const int64_t* gj,
                             const void* W, const float* bias, int act, const Dropout& dp,
                             void* out, bool out_bf16, hipStream_t s) {
-  if (!skinny_enabled() || P < 1024 || P >= (1ll << 31) || gi == nullptr || gj == nullptr) return 0;
+  if (skinny_pair_linear_bf16_route(P, K, N, G, ldg, gi, G2, ldg2, gj, W, out) == route::kTiled)
+    return route::kTiled;
   if (G2 == nullptr) { G2 = G; ldg2 = ldg; }
-  if (ldg % 8 || ldg2 % 8 || (((uintptr_t)G | (uintptr_t)G2 | (uintptr_t)W | (uintptr_t)out) & 15))
-    return 0;
   const dim3 grid(proj_grid(P, sk::kPairWaves)), block(64 * sk::kPairWaves);
 #define SKPB(k, n)                                                                              \
   if (K == k && N == n) {                                                                       \
@@ -2002,13 +2044,16 @@ int skinny_pair_linear_bf16(int64_t P, int64_t K, int64_t N, const void* G, int6
 // dX (M x N) = (dh + d1 (x) a1 [+ d2 (x) a2]) W^T with W (N, K) row-major (the
 // projection's input gradient): K, N in {64, 128}, hF >= 16 dividing K, C row-major
 // (ldc = N); 0 = not covered (the caller runs the tiled head-outer GEMM)
+int skinny_dx_route(int64_t M, int64_t N, int64_t K, const void* Dh, const void* W, const void* C,
+                    int hH, int hF, const void* d1, const void* a1) {
+  return route::dx(skinny_enabled(), M, N, K, (uintptr_t)Dh, (uintptr_t)W, (uintptr_t)C, hH, hF,
+                   d1 != nullptr && a1 != nullptr);
+}
+
 int skinny_dx(int64_t M, int64_t N, int64_t K, const float* Dh, const float* W, float* C,
               int hH, int hF, const float* d1, const float* a1, const float* d2, const float* a2,
               hipStream_t s) {
-  if (!skinny_enabled() || M < 1024 || M * K * 4 >= (1ll << 31) || M * hH * 4 >= (1ll << 31))
-    return 0;
-  if (hF < 16 || K % hF != 0 || (int64_t)hH * hF != K || d1 == nullptr || a1 == nullptr) return 0;
-  if (((uintptr_t)Dh | (uintptr_t)C | (uintptr_t)W) & 15) return 0;
+  if (skinny_dx_route(M, N, K, Dh, W, C, hH, hF, d1, a1) == route::kTiled) return route::kTiled;
   const dim3 grid(proj_grid(M)), block(64 * sk::kProjWaves);
 #define SKDX(k, n)                                                                              \
   if (K == k && N == n) {                                                                       \
@@ -2121,6 +2166,37 @@ int skinny_wgrad(int64_t M, int64_t N, int64_t K, const float* A, int64_t sAm, i
 extern "C" int32_t msha_wgrad_kernel(int32_t mode) {
   if (mode != 0 && mode != 1 && mode != 3) return msha::wgrad_mode().load();
   return msha::wgrad_mode().exchange(mode);
+}
+
+// host-only (ABI 16, added): the routes of the resident-W kernels, from the functions the
+// launches themselves ask (skinny_route.h); nothing is launched
+extern "C" int32_t msha_project_scores_route(int64_t M, int64_t K, int32_t heads, int32_t feat,
+                                             int32_t dtype, const void* X, const void* W,
+                                             const float* al, const float* ar, const void* h,
+                                             int32_t* sched) {
+  if (sched != nullptr) sched[0] = sched[1] = sched[2] = 0;
+  if (M <= 0 || K <= 0 || heads <= 0 || feat <= 0) return msha::route::kTiled;
+  if (dtype == MSHA_DTYPE_BF16)
+    return msha::project_go<msha::bf16_t>(false, sched, M, K, heads, feat, X, W, al, ar,
+                                          const_cast<void*>(h), nullptr, nullptr, nullptr);
+  if (dtype != MSHA_DTYPE_F32) return msha::route::kTiled;
+  return msha::project_go<float>(false, sched, M, K, heads, feat, X, W, al, ar,
+                                 const_cast<void*>(h), nullptr, nullptr, nullptr);
+}
+
+extern "C" int32_t msha_pair_linear_route(int64_t n_pairs, int64_t K, int64_t N, const float* G,
+                                          int64_t ldg, const int64_t* gi, const float* G2,
+                                          int64_t ldg2, const int64_t* gj, int64_t g_rows,
+                                          int64_t g2_rows, const float* W, const float* out) {
+  return msha::skinny_pair_linear_route(n_pairs, K, N, G, ldg, gi, G2, ldg2, gj, g_rows, g2_rows,
+                                        W, out).code;
+}
+
+extern "C" int32_t msha_pair_linear_bf16_route(int64_t n_pairs, int64_t K, int64_t N, const void* G,
+                                               int64_t ldg, const int64_t* gi, const void* G2,
+                                               int64_t ldg2, const int64_t* gj, const void* W,
+                                               const void* out) {
+  return msha::skinny_pair_linear_bf16_route(n_pairs, K, N, G, ldg, gi, G2, ldg2, gj, W, out);
 }
 
 extern "C" int msha_debug_timeline(void* buf, int64_t slots) {
