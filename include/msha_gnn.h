@@ -331,6 +331,38 @@ MSHA_API int msha_edge_attention_bwd_fused_ex(
     const float* uc, const float* qc, float* d_el, float* d_er, void* d_hc, float* de, void* ws,
     size_t ws_bytes, msha_stream_t stream);
 
+/* The column pass with the projection's weight gradient inside (ABI 16, added: new symbols
+ * only, MSHA_ABI_VERSION stays 16).  Precondition: the graph is square and hc is the
+ * projection's own output, hc = h = X W (row j of the projection is column j of the
+ * attention), X (n_cols, K = 128) fp32 with row pitch ldx floats, a_l, a_r (heads * feat)
+ * fp32, all 16-byte aligned.  Arguments and outputs as msha_edge_attention_bwd_fused_ex with
+ * row terms (uc, qc required; d_el, d_er, d_hc are the same bits); in addition the column
+ * pass leaves, in wg_ws, nb slabs of 128 x 128 floats (block b: X^T D' over its columns,
+ * D'_j = d_hc_j + d_el_j (x) a_l + d_er_j (x) a_r) and the partial sums of d_el (x) h and
+ * d_er (x) h; msha_wgrad_reduce adds them in block order into dW (128 x 128, pitch ldc), dal
+ * and dar (heads * feat).  cut (nb + 1 int32, device): the blocks' column ranges,
+ * msha_col_ranges over a host copy of colptr (int64) -- a function of the graph and nb only,
+ * so results repeat bit for bit.  nb = msha_edge_attention_bwd_fused_wgrad_route(...), a
+ * host-only query (rowterms / er_table: the call has row terms / reads the er table, not
+ * a_r); 0 = not covered (fp32, heads x feat = 8 x 16, 4 x 32, 2 x 64 or 1 x 128, K 128, no multi-chunk column, tables under
+ * 2 GiB, MSHA_BWD_WGRAD != 0) and the entry returns MSHA_ERR_UNSUPPORTED: the caller runs
+ * msha_edge_attention_bwd_fused_ex and its own weight gradient. */
+MSHA_API int32_t msha_edge_attention_bwd_fused_wgrad_route(
+    const msha_graph* g, int32_t heads, int32_t feat, int32_t dtype, int64_t K, int64_t ldx,
+    int32_t rowterms, int32_t er_table, const void* X, const float* al, const float* ar);
+MSHA_API int32_t msha_col_range_blocks(int64_t n_cols); /* the nb the route answers with */
+MSHA_API int msha_col_ranges(const int64_t* colptr, int64_t n_cols, int32_t nb, int32_t* cut);
+MSHA_API size_t msha_edge_attention_bwd_fused_wgrad_workspace_size(int32_t nb);
+MSHA_API int msha_edge_attention_bwd_fused_wgrad(
+    const msha_graph* g, int32_t heads, int32_t feat, int32_t dtype, const float* el,
+    const float* er, const void* hc, const float* lse, const void* u, const void* u_lo,
+    const void* dU, float neg_slope, float drop_p, uint64_t seed, uint64_t offset,
+    const float* uc, const float* qc, float* d_el, float* d_er, void* d_hc, float* de, void* ws,
+    size_t ws_bytes, const void* X, int64_t ldx, int64_t K, const float* a_l, const float* a_r,
+    const int32_t* cut, int32_t nb, void* wg_ws, size_t wg_ws_bytes, msha_stream_t stream);
+MSHA_API int msha_wgrad_reduce(const void* wg_ws, int32_t nb, float* dW, int64_t ldc, float* dal,
+                               float* dar, msha_stream_t stream);
+
 /* Scores from the gathered row (ABI 9).  Every caller of the u = att @ hc path scores
  * the gathered table itself: er[j,h] = hc[j,h,:] . a_r[h,:] (Ablation.py:266-267 --
  * a[:F] against h1_j, the rows u aggregates).  Given a_r ((heads, feat) fp32, 16-byte

@@ -132,6 +132,15 @@ SIGNATURES = {
                                              P, P, P, P, P, P]),
     "msha_edge_attention_bwd_fused_ex": (C.c_int, [GP, I32, I32, I32, P, P, P, P, P, P, P, F32,
                                                    F32, U64, U64, P, P, P, P, P, P, P, SZ, P]),
+    "msha_edge_attention_bwd_fused_wgrad_route": (I32, [GP, I32, I32, I32, I64, I64, I32, I32, P,
+                                                        P, P]),
+    "msha_col_range_blocks": (I32, [I64]),
+    "msha_col_ranges": (C.c_int, [P, I64, I32, P]),
+    "msha_edge_attention_bwd_fused_wgrad_workspace_size": (SZ, [I32]),
+    "msha_edge_attention_bwd_fused_wgrad": (C.c_int, [GP, I32, I32, I32, P, P, P, P, P, P, P, F32,
+                                                      F32, U64, U64, P, P, P, P, P, P, P, SZ, P,
+                                                      I64, I64, P, P, P, I32, P, SZ, P]),
+    "msha_wgrad_reduce": (C.c_int, [P, I32, P, I64, P, P, P]),
     "msha_edge_attention_row_scores_supported": (C.c_int, [GP, I32, I32, I32]),
     "msha_edge_attention_row_scores_preferred": (C.c_int, [GP, I32, I32, I32]),
     "msha_edge_attention_fwd_rs": (C.c_int, [GP, I32, I32, I32, P, P, P, F32, F32, U64, U64, P,

@@ -375,6 +375,10 @@ int skinny_wgrad(int64_t M, int64_t N, int64_t K, const float* A, int64_t sAm, i
                  float* cs_out1 = nullptr, float* cs_out2 = nullptr,
                  const float* cs_w = nullptr, int64_t ldw = 0);
 
+// wgrad_reduce_kernel alone over slabs / partials in wgrad_kernel's layouts
+void skinny_wgrad_reduce(const float* slab, int nb, float* C, int64_t ldc, const float* cpart,
+                         float* cs1, float* cs2, hipStream_t s);
+
 // Welford triple (count, mean, M2) and Chan's combination (bn.hip, head.hip)
 struct Wf {
   float n, mean, m2;

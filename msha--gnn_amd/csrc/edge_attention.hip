@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "col_ranges.h"
 #include "edge_geo.h"
 
 #ifndef COLS_EH
@@ -1232,6 +1233,449 @@ __global__ void __launch_bounds__(256) bwd_cols_eh_kernel(
   }
 }
 
+// The head-per-lane column pass with the projection's weight gradient inside, for square
+// graphs whose gathered table is the projection's own output (hc = h = X W): row j of the
+// weight gradient's operand, D'_j = d_hc_j + d_el_j (x) a_l + d_er_j (x) a_r, needs only
+// what this pass produces for column j and the d_el the row statistics wrote before it.
+// Persistent grid: block b owns columns [cut[b], cut[b+1]) (col_ranges.h) and walks them in
+// tiles of kFwTile columns.  Block = 12 gather waves + 4 matrix waves (one per SIMD).
+// Gather wave w takes columns w, w + 12, ... of a tile with bwd_cols_eh_kernel's per-column
+// code (same loads, same operation order: d_hc, d_er and de are the same bits).  Next to
+// hc_j it loads X_j and h_j (8 bytes a lane), and at the column's end it parks X_j and D'_j
+// (wgrad_kernel's order: fmaf(e2, a2, fmaf(e1, a1, d))) in one of two LDS tiles and adds
+// d_el_j h_j, d_er_j h_j to its score-vector sums.  One block barrier per tile; between two
+// barriers the gather waves fill tile t while matrix wave m adds tile t - 1's X^T D' into
+// its 64 x 64 quarter of dW (v_mfma_f32_32x32x2_f32, rows ascending, 64 accumulators that
+// live for the whole block).  Block end: slab[b] and cpart[which][n][b] in
+// wgrad_reduce_kernel's layouts.  No wait on another block, no atomics.
+constexpr int kFwWaves = 16, kFwGather = 12;
+#ifndef FW_TILE
+#define FW_TILE 48
+#endif
+constexpr int kFwTile = FW_TILE;  // columns per tile (kFwTile / 12 per gather wave and barrier)
+static_assert(kFwTile % kFwGather == 0 && kFwTile % 2 == 0 && kFwTile * 128 >= kFwGather * 256,
+              "tile geometry");
+
+typedef float fw_f32x16 __attribute__((ext_vector_type(16)));
+
+// Matrix wave mw: quarter (m0, n0) of dW.  Tile t - 1 between barriers t - 1 and t; rows k,
+// k + 1 of a tile per step: lane (i, q) gives X[k + q, m0 + 32 t + i], D'[k + q, n0 + 32 u + i].
+// Ends with the quarter's store into out (the block's slab) and the block's two last barriers.
+__device__ __forceinline__ void fw_matrix_wave(const float* xs, const float* ds, int ntiles, int mw,
+                                               int lane, float* __restrict__ out) {
+  const int m0 = 64 * (mw >> 1), n0 = 64 * (mw & 1);
+  fw_f32x16 wacc[2][2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) wacc[t][u][v] = 0.f;
+  for (int tile = 0; tile <= ntiles; ++tile) {
+    if (tile > 0) {
+      const int buf = (tile - 1) & 1;
+      const float* xa = xs + (buf * kFwTile + (lane >> 5)) * 128 + m0 + (lane & 31);
+      const float* db = ds + (buf * kFwTile + (lane >> 5)) * 128 + n0 + (lane & 31);
+#pragma unroll 4
+      for (int k = 0; k < kFwTile; k += 2) {
+        const float a[2] = {xa[k * 128], xa[k * 128 + 32]};
+        const float b[2] = {db[k * 128], db[k * 128 + 32]};
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int u = 0; u < 2; ++u)
+            wacc[t][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[u], wacc[t][u], 0, 0, 0);
+      }
+    }
+    if (tile < ntiles) __syncthreads();
+  }
+  // 32x32 C layout: reg v of lane l is row 8 (v / 4) + 4 (l >> 5) + (v % 4), col l & 31
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        out[(m0 + 32 * t + 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3)) * 128 + n0 + 32 * u +
+            (lane & 31)] = wacc[t][u][v];
+  __syncthreads();  // the gather waves' score-vector sums
+  __syncthreads();
+}
+
+// Column end of a gather wave: d_hc_j lies in the wave's LDS row drow (written by the lanes
+// that stored it to global); lane l turns its columns n2, n2 + 1 into D'_j (wgrad_kernel's
+// order), parks X_j beside it and adds the score-vector terms.  The row passes through the
+// wave's own LDS slot (a wave's LDS operations execute in order).
+__device__ __forceinline__ void fw_park(float* xrow, float* drow, const float* avs, int n2, float e1,
+                                        float e2, float2 xv, float2 hv2, float2& cs1, float2& cs2) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  float2 dd = *reinterpret_cast<const float2*>(drow + n2);
+  const float2 al2 = *reinterpret_cast<const float2*>(avs + n2);
+  const float2 ar2 = *reinterpret_cast<const float2*>(avs + 128 + n2);
+  dd.x = fmaf(e2, ar2.x, fmaf(e1, al2.x, dd.x));
+  dd.y = fmaf(e2, ar2.y, fmaf(e1, al2.y, dd.y));
+  *reinterpret_cast<float2*>(drow + n2) = dd;
+  *reinterpret_cast<float2*>(xrow + n2) = xv;
+  cs1.x = fmaf(e1, hv2.x, cs1.x);
+  cs1.y = fmaf(e1, hv2.y, cs1.y);
+  cs2.x = fmaf(e2, hv2.x, cs2.x);
+  cs2.y = fmaf(e2, hv2.y, cs2.y);
+}
+
+// Block end of the gather waves: score-vector sums, waves in order; cpart[which][n][block].
+// csred ([wave][which][128]) reuses the X tiles once the matrix waves have read the last one.
+__device__ __forceinline__ void fw_finish(float* csred, int w, int n2, float2 cs1, float2 cs2,
+                                          float* __restrict__ cpart) {
+  __syncthreads();
+  *reinterpret_cast<float2*>(csred + (w * 2 + 0) * 128 + n2) = cs1;
+  *reinterpret_cast<float2*>(csred + (w * 2 + 1) * 128 + n2) = cs2;
+  __syncthreads();
+  if (threadIdx.x < 256) {
+    float v = 0.f;
+#pragma unroll
+    for (int k = 0; k < kFwGather; ++k) v += csred[k * 256 + threadIdx.x];
+    cpart[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = v;
+  }
+}
+
+template <int H, int F>
+__global__ void __launch_bounds__(64 * kFwWaves) bwd_cols_wgrad_kernel(
+    const int32_t* __restrict__ cut, const int32_t* __restrict__ colptr,
+    const int32_t* __restrict__ csc_row, const int32_t* __restrict__ csc_eid, int64_t n_edges,
+    const uint8_t* __restrict__ rowflag, int64_t n_rows, const float* __restrict__ rec,
+    const float* __restrict__ er, const float* __restrict__ hc, const float* __restrict__ dU,
+    float slope, Dropout dp, bool slot_de, float* __restrict__ de, float* __restrict__ d_hc,
+    float* __restrict__ d_er, const float* __restrict__ X, int64_t ldx,
+    const float* __restrict__ a_l, const float* __restrict__ a_r, const float* __restrict__ d_el,
+    float* __restrict__ slab, float* __restrict__ cpart) {
+  using T = float;
+  using G = Geo<H, F, T>;
+  static_assert(G::D == 128 && G::V == 4, "128 fp32 per row");
+  constexpr int NV = G::QH;
+  constexpr int NG = COLS_NG;
+  __shared__ __attribute__((aligned(16))) float xs[2 * kFwTile * 128];  // X_j, by tile slot
+  __shared__ __attribute__((aligned(16))) float ds[2 * kFwTile * 128];  // D'_j
+  __shared__ __attribute__((aligned(16))) float avs[2 * 128];            // a_l, a_r
+  const int lane = lane_id();
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int e_s = lane / H, h_s = lane % H;
+  const rsrc_t r_row = make_rsrc(csc_row, (uint32_t)(n_edges * 4));
+  const rsrc_t r_eid = make_rsrc(csc_eid, (uint32_t)(n_edges * 4));
+  const rsrc_t r_flag = make_rsrc(rowflag, (uint32_t)n_rows);
+  const rsrc_t r_rec = make_rsrc(rec, (uint32_t)(n_rows * 4 * rec_stride(H)));
+  const rsrc_t r_dU = make_rsrc(dU, (uint32_t)(n_rows * G::D * sizeof(T)));
+  const rsrc_t r_de = make_rsrc(de, (uint32_t)(n_edges * 4 * H));
+  const uint32_t h_off = h_s * F * sizeof(T);
+  const bool need_eid = dp.active || (de != nullptr && !slot_de);
+  const int c0 = cut[blockIdx.x], c1 = cut[blockIdx.x + 1];
+
+  // weight-gradient side: lane l holds columns n = 2l, 2l + 1 of a row (head n / F)
+  const int n2 = 2 * lane, hh = n2 / F;
+  const int ntiles = (c1 - c0 + kFwTile - 1) / kFwTile;
+  if (threadIdx.x < 256) avs[threadIdx.x] = (threadIdx.x < 128 ? a_l : a_r - 128)[threadIdx.x];
+  __syncthreads();
+  if (w >= kFwGather) {
+    fw_matrix_wave(xs, ds, ntiles, w - kFwGather, lane, slab + (int64_t)blockIdx.x * (128 * 128));
+    return;
+  }
+  float2 cs1 = make_float2(0.f, 0.f), cs2 = cs1;
+
+  // the wave's columns in order: slot w + 12 r of tile t is column c0 + t kFwTile + slot
+  int32_t ii[NG];
+  {
+    const int32_t jf = c0 + w;
+    const int32_t s0f = jf < c1 ? colptr[jf] : 0, s1f = jf < c1 ? colptr[jf + 1] : 0;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int32_t a = s0f + g * G::CE + e_s;
+      ii[g] = buf_i32(r_row, a < s1f ? (uint32_t)a * 4u : kOOB);
+    }
+  }
+  int tile = 0;
+  for (int32_t base = c0; base < c1; base += kFwTile, ++tile) {
+    const int buf = tile & 1;
+    for (int slot = w; slot < kFwTile; slot += kFwGather) {
+      const int32_t jc = base + slot;
+      float* xrow = xs + (buf * kFwTile + slot) * 128;
+      float* drow = ds + (buf * kFwTile + slot) * 128;
+      if (jc >= c1) {  // past the range: a zero row (adds 0)
+        *reinterpret_cast<float2*>(xrow + n2) = make_float2(0.f, 0.f);
+        *reinterpret_cast<float2*>(drow + n2) = make_float2(0.f, 0.f);
+        continue;
+      }
+      // this wave's next column (its CSC rows are loaded at this column's end)
+      const int32_t njc = slot + kFwGather < kFwTile ? jc + kFwGather : base + kFwTile + w;
+      const bool has_next = njc < c1;
+      const int32_t s0 = colptr[jc], s1 = colptr[jc + 1];
+      const int32_t ns0 = has_next ? colptr[njc] : 0;
+      const int32_t ns1 = has_next ? colptr[njc + 1] : 0;
+      Pk<T> hcv[NV], acc[NV];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        hcv[k] = pk_load(hc + (int64_t)jc * G::D + h_s * F + G::V * k);
+        acc[k] = pk_zero<T>();
+      }
+      const float er_tab = er[(int64_t)jc * H + h_s];
+      const float2 xv = *reinterpret_cast<const float2*>(X + (int64_t)jc * ldx + n2);
+      const float2 hv2 = *reinterpret_cast<const float2*>(hc + (int64_t)jc * G::D + n2);
+      const float e1 = d_el[(int64_t)jc * H + hh];
+      float xacc = 0.f;
+      for (int32_t cs = s0; cs < s1; cs += NG * G::CE) {
+        Pk<T> dUv[NG][NV];
+        int32_t eid[NG];
+        float r_el[NG], r_lse[NG], Dsi[NG];
+        uint32_t vflag[NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          const bool valid = cs + g * G::CE + e_s < s1;
+          const uint32_t row_off = valid ? (uint32_t)ii[g] * (G::D * sizeof(T)) + h_off : kOOB;
+#pragma unroll
+          for (int k = 0; k < NV; ++k)
+            dUv[g][k] = pk_load_buf(r_dU, row_off + (valid ? k * 16u : 0u), (T*)nullptr);
+          eid[g] = buf_i32(r_eid, valid && need_eid ? (uint32_t)(cs + g * G::CE + e_s) * 4u : kOOB);
+          const uint32_t rec_off = valid ? (uint32_t)ii[g] * (4u * rec_stride(H)) + h_s * 4u : kOOB;
+          r_el[g] = buf_f32(r_rec, rec_off);
+          r_lse[g] = buf_f32(r_rec, valid ? rec_off + 4u * H : kOOB);
+          Dsi[g] = buf_f32(r_rec, valid ? rec_off + 8u * H : kOOB);
+          if constexpr (rec_has_flag(H))
+            vflag[g] = __float_as_uint(buf_f32(r_rec, valid ? rec_off - h_s * 4u + 12u * H : kOOB));
+          else
+            vflag[g] = buf_u8(r_flag, valid ? (uint32_t)ii[g] : kOOB);
+        }
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          const int32_t a = cs + (NG + g) * G::CE + e_s;
+          ii[g] = buf_i32(r_row, a < s1 ? (uint32_t)a * 4u : kOOB);
+        }
+        const float erh = er_tab;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          const int32_t sl = cs + g * G::CE + e_s;
+          const bool valid = sl < s1;
+          const bool virt = vflag[g] != 0;
+          const float pre = r_el[g] + erh;
+          const float sv = virt ? 0.f : lrelu(pre, slope);
+          const float att = __expf(sv - r_lse[g]);
+          const float dropf = dropout_factor(dp, (uint64_t)eid[g] * H + h_s);
+          const float wv = valid ? att * dropf : 0.f;
+          float d[NV];
+#pragma unroll
+          for (int k = 0; k < NV; ++k) {
+            d[k] = pk_dot(dUv[g][k], hcv[k]);
+            acc[k] = pk_fma(wv, dUv[g][k], acc[k]);
+          }
+#pragma unroll
+          for (int o = 1; o < NV; o <<= 1)
+#pragma unroll
+            for (int k = 0; k < NV; k += 2 * o) d[k] = d[k] + d[k + o];
+          const float dsv = att * (d[0] * dropf - Dsi[g]);
+          const float dev = virt ? 0.f : dsv * (pre > 0.f ? 1.f : slope);
+          const uint32_t at = slot_de ? (uint32_t)sl : (uint32_t)eid[g];
+          buf_store_f32(r_de, valid ? at * (4u * H) + h_s * 4u : kOOB, dev);
+          xacc += valid ? dev : 0.f;
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const int32_t a = ns0 + g * G::CE + e_s;
+        ii[g] = buf_i32(r_row, a < ns1 ? (uint32_t)a * 4u : kOOB);
+      }
+#pragma unroll
+      for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int o = H; o < 64; o <<= 1) acc[k] = pk_xor_add(acc[k], o);
+      if (e_s == 0) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+          pk_store(d_hc + (int64_t)jc * G::D + h_s * F + G::V * k, acc[k]);
+          pk_store(drow + h_s * F + G::V * k, acc[k]);
+        }
+      }
+      xacc = wave_xor_sum<H>(xacc);
+      if (lane < H) d_er[(int64_t)jc * H + lane] = xacc;
+      fw_park(xrow, drow, avs, n2, e1, __shfl(xacc, hh), xv, hv2, cs1, cs2);
+    }
+    __syncthreads();
+  }
+  fw_finish(xs, w, n2, cs1, cs2, cpart);
+}
+
+// The same for the shapes of the quad-per-lane column pass (fp32 heads wider than 64 bytes:
+// 4 x 32, 2 x 64, 1 x 128; one 16-byte piece of the row per lane, EPI edges per gather
+// instruction): bwd_cols_kernel<H, F, float, true>'s per-column code -- same loads through the
+// buffer descriptor, same operation order, so d_hc and d_er are the same bits -- inside
+// bwd_cols_wgrad_kernel's block.  Row terms only (no de store).
+template <int H, int F>
+__global__ void __launch_bounds__(64 * kFwWaves) bwd_cols_wgrad_q_kernel(
+    const int32_t* __restrict__ cut, const int32_t* __restrict__ colptr,
+    const int32_t* __restrict__ csc_row, const int32_t* __restrict__ csc_eid,
+    const uint8_t* __restrict__ rowflag, int64_t n_rows, const float* __restrict__ rec,
+    const float* __restrict__ er, const float* __restrict__ hc, const float* __restrict__ dU,
+    float slope, Dropout dp, float* __restrict__ d_hc, float* __restrict__ d_er,
+    const float* __restrict__ X, int64_t ldx, const float* __restrict__ a_l,
+    const float* __restrict__ a_r, const float* __restrict__ d_el, float* __restrict__ slab,
+    float* __restrict__ cpart) {
+  using T = float;
+  using G = Geo<H, F, T>;
+  static_assert(G::D == 128 && G::V == 4 && G::QPL == 1, "128 fp32 per row, one piece per lane");
+  __shared__ __attribute__((aligned(16))) float xs[2 * kFwTile * 128];  // X_j, by tile slot
+  __shared__ __attribute__((aligned(16))) float ds[2 * kFwTile * 128];  // D'_j
+  __shared__ __attribute__((aligned(16))) float avs[2 * 128];            // a_l, a_r
+  const int lane = lane_id();
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int e_s = lane / H, h_s = lane % H;
+  const int g_e = lane / G::NQ;
+  const int c0 = cut[blockIdx.x], c1 = cut[blockIdx.x + 1];
+  const int n2 = 2 * lane, hh = n2 / F;
+  const int ntiles = (c1 - c0 + kFwTile - 1) / kFwTile;
+  if (threadIdx.x < 256) avs[threadIdx.x] = (threadIdx.x < 128 ? a_l : a_r - 128)[threadIdx.x];
+  __syncthreads();
+  if (w >= kFwGather) {
+    fw_matrix_wave(xs, ds, ntiles, w - kFwGather, lane, slab + (int64_t)blockIdx.x * (128 * 128));
+    return;
+  }
+  float2 cs1 = make_float2(0.f, 0.f), cs2 = cs1;
+  const rsrc_t r_dU = make_rsrc(dU, (uint32_t)(n_rows * G::D * sizeof(T)));
+  const int q = lane % G::NQ;
+
+  // CSC slot rows two slot groups ahead, as bwd_cols_kernel
+  int32_t i0 = 0, i1 = 0;
+  if (c0 + w < c1) {
+    const int32_t s0f = colptr[c0 + w], s1f = colptr[c0 + w + 1];
+    i0 = s0f + e_s < s1f ? csc_row[s0f + e_s] : 0;
+    i1 = s0f + G::CE + e_s < s1f ? csc_row[s0f + G::CE + e_s] : 0;
+  }
+  int tile = 0;
+  for (int32_t base = c0; base < c1; base += kFwTile, ++tile) {
+    const int buf = tile & 1;
+    for (int slot_t = w; slot_t < kFwTile; slot_t += kFwGather) {
+      const int32_t jc = base + slot_t;
+      float* xrow = xs + (buf * kFwTile + slot_t) * 128;
+      float* drow = ds + (buf * kFwTile + slot_t) * 128;
+      if (jc >= c1) {  // past the range: a zero row (adds 0)
+        *reinterpret_cast<float2*>(xrow + n2) = make_float2(0.f, 0.f);
+        *reinterpret_cast<float2*>(drow + n2) = make_float2(0.f, 0.f);
+        continue;
+      }
+      const int32_t njc = slot_t + kFwGather < kFwTile ? jc + kFwGather : base + kFwTile + w;
+      const bool has_next = njc < c1;
+      const int32_t s0 = colptr[jc], s1 = colptr[jc + 1];
+      const int32_t ns0 = has_next ? colptr[njc] : 0;
+      const int32_t ns1 = has_next ? colptr[njc + 1] : 0;
+      const Pk<T> hcq = pk_load(hc + (int64_t)jc * G::D + G::V * q);
+      Pk<T> acc = pk_zero<T>();
+      const float erh = er[(int64_t)jc * H + h_s];
+      const float2 xv = *reinterpret_cast<const float2*>(X + (int64_t)jc * ldx + n2);
+      const float2 hv2 = *reinterpret_cast<const float2*>(hc + (int64_t)jc * G::D + n2);
+      const float e1 = d_el[(int64_t)jc * H + hh];
+      float xacc = 0.f;
+      for (int32_t cs = s0; cs < s1; cs += G::CE) {
+        const int32_t slot = cs + e_s;
+        const bool valid = slot < s1;
+        const int32_t i = i0;
+        const int64_t eid = valid ? (int64_t)csc_eid[slot] : 0;
+        float pre = 0.f, att = 0.f, dropf = 0.f, Dsi = 0.f;
+        bool virt = false;
+        if (valid) {
+          const float* r = rec + (int64_t)i * rec_stride(H);
+          virt = rowflag != nullptr && rowflag[i] != 0;
+          pre = r[h_s] + erh;
+          const float sv = virt ? 0.f : lrelu(pre, slope);
+          att = __expf(sv - r[H + h_s]);
+          Dsi = r[2 * H + h_s];
+          dropf = dropout_factor(dp, (uint64_t)eid * H + h_s);
+        }
+        const float wv = att * dropf;
+        const int nvalid = min(G::CE, (int)(s1 - cs));
+        float gsum = 0.f;
+        if constexpr (G::EPI == 1 || COLS_EPI_BUF) {
+          // UG gather instructions in flight, consumed in slot order (bwd_cols_kernel)
+          constexpr int UG = G::EPI == 1 ? COLS_WIDE_UG : COLS_NARROW_UG;
+#pragma unroll
+          for (int g0 = 0; g0 < G::CE; g0 += UG * G::EPI) {
+            if (g0 >= nvalid) break;
+            u32x4_t dl[UG];
+#pragma unroll
+            for (int u = 0; u < UG; ++u) {
+              const int g = g0 + u * G::EPI;
+              if (g >= G::CE) break;
+              const int ei = g + g_e;
+              const int32_t iq = __shfl(i, ei * H);
+              const uint32_t off = ei < nvalid
+                  ? (uint32_t)iq * (uint32_t)(G::D * sizeof(T)) + (uint32_t)(G::V * q * sizeof(T))
+                  : kOOB;
+              dl[u] = buf_b128(r_dU, off);
+            }
+#pragma unroll
+            for (int u = 0; u < UG; ++u) {
+              const int g = g0 + u * G::EPI;
+              if (g >= G::CE || g >= nvalid) break;
+              const int ei = g + g_e;
+              const bool mine = e_s >= g && e_s < g + G::EPI;
+              const int srcl = ((e_s - g) & (G::EPI - 1)) * G::NQ + h_s * G::QH;
+              const float wq = __shfl(wv, ei * H + q / G::QH);
+              const Pk<T> dUi = pk_from_raw(dl[u], (T*)nullptr);
+              acc = pk_fma(wq, dUi, acc);
+              float t = pk_dot(dUi, hcq);
+              t = group_sum<G::QH>(t);
+              const float cand = __shfl(t, srcl);
+              if (mine) gsum = cand;
+            }
+          }
+        } else {
+#pragma unroll
+          for (int g = 0; g < G::CE; g += G::EPI) {
+            if (g >= nvalid) break;
+            const int ei = g + g_e;
+            const int32_t iq = __shfl(i, ei * H);
+            const bool mine = e_s >= g && e_s < g + G::EPI;
+            const int srcl = ((e_s - g) & (G::EPI - 1)) * G::NQ + h_s * G::QH;
+            const float wq = __shfl(wv, ei * H + q / G::QH);
+            float t = 0.f;
+            if (ei < nvalid) {
+              const Pk<T> dUi = pk_load(dU + (int64_t)iq * G::D + G::V * q);
+              acc = pk_fma(wq, dUi, acc);
+              t = pk_dot(dUi, hcq);
+            }
+            t = group_sum<G::QH>(t);
+            const float cand = __shfl(t, srcl);
+            if (mine) gsum = cand;
+          }
+        }
+        const int32_t sl2 = slot + 2 * G::CE;
+        const int32_t i2 = sl2 < s1 ? csc_row[sl2] : 0;
+        if (valid) {
+          const float dsv = att * (gsum * dropf - Dsi);
+          const float dev = virt ? 0.f : dsv * (pre > 0.f ? 1.f : slope);
+          xacc += dev;
+        }
+        i0 = i1;
+        i1 = i2;
+      }
+      if (has_next) {
+        const int32_t a0 = ns0 + e_s, a1 = ns0 + G::CE + e_s;
+        i0 = a0 < ns1 ? csc_row[a0] : 0;
+        i1 = a1 < ns1 ? csc_row[a1] : 0;
+      }
+      if (G::EPI > 1) {
+#pragma unroll
+        for (int o = G::NQ; o < 64; o <<= 1) acc = pk_xor_add(acc, o);
+      }
+      if (g_e == 0) {
+        pk_store(d_hc + (int64_t)jc * G::D + G::V * q, acc);
+        pk_store(drow + G::V * q, acc);
+      }
+      xacc = wave_xor_sum<H>(xacc);
+      if (lane < H) d_er[(int64_t)jc * H + lane] = xacc;
+      fw_park(xrow, drow, avs, n2, e1, __shfl(xacc, hh), xv, hv2, cs1, cs2);
+    }
+    __syncthreads();
+  }
+  fw_finish(xs, w, n2, cs1, cs2, cpart);
+}
+
 // d_el[i] = sum over the row's edges of de.  Lane = (row slot, head): 64/H rows per
 // wave, each lane walking its row's edges with independent loads.  The sum keeps
 // bwd_rows' order (lane e_s of a CE-edge chunk accumulates edges e_s, e_s + CE, ...;
@@ -1679,6 +2123,96 @@ extern "C" int msha_edge_attention_bwd_fused_ex(
     launch_bwd_fused<float>(g, heads, feat, el, er, nullptr, hc, lse, u, nullptr, dU, neg_slope, dp,
                             d_el, d_er, d_hc, de, rec, part, part_x, uc, qc, s);
   return check_launch("edge_attention_bwd_fused");
+}
+
+// ------------------------------------- column pass with the weight gradient inside ---
+// MSHA_BWD_WGRAD=0: the route query answers no (A/B only); read per call
+static int fused_wgrad_blocks(const msha_graph* g, int32_t heads, int32_t feat, int32_t dtype,
+                              int64_t K, int64_t ldx, bool rowterms, bool er_table, const void* X,
+                              const float* al, const float* ar) {
+  if (g == nullptr || g->colptr == nullptr) return 0;
+  return colrange::route(env_int("MSHA_BWD_WGRAD", 1) != 0, g->n_rows, g->n_cols, g->n_edges,
+                         g->n_multi, heads, feat, dtype == MSHA_DTYPE_F32, K, ldx, rowterms,
+                         er_table, COLS_EH && env_int("MSHA_COLS_NOBUF", 0) != 1,
+                         rec_stride(heads), (uintptr_t)X, (uintptr_t)al, (uintptr_t)ar);
+}
+
+// host-only: the block count the fused entry would run with, 0 = it would refuse
+extern "C" int32_t msha_edge_attention_bwd_fused_wgrad_route(
+    const msha_graph* g, int32_t heads, int32_t feat, int32_t dtype, int64_t K, int64_t ldx,
+    int32_t rowterms, int32_t er_table, const void* X, const float* al, const float* ar) {
+  return fused_wgrad_blocks(g, heads, feat, dtype, K, ldx, rowterms != 0, er_table != 0, X, al, ar);
+}
+
+// host-only: the block count of the fused pass on a graph of n_cols columns
+extern "C" int32_t msha_col_range_blocks(int64_t n_cols) { return colrange::blocks_for(n_cols); }
+
+// host-only: cut[0..nb] from a host copy of colptr (col_ranges.h)
+extern "C" int msha_col_ranges(const int64_t* colptr, int64_t n_cols, int32_t nb, int32_t* cut) {
+  MSHA_ARG_CHECK(colptr && cut && n_cols > 0 && nb > 0 && nb <= n_cols &&
+                     nb <= colrange::kMaxBlocks,
+                 "col_ranges: need 0 < nb <= min(n_cols, 256)");
+  colrange::cut(colptr, n_cols, (int)nb, cut);
+  return MSHA_OK;
+}
+
+// nb slabs of 128 x 128 floats, then the score-vector partials [2][128][nb]
+extern "C" size_t msha_edge_attention_bwd_fused_wgrad_workspace_size(int32_t nb) {
+  return nb > 0 ? (size_t)nb * (128 * 128 + 256) * sizeof(float) : 0;
+}
+
+extern "C" int msha_edge_attention_bwd_fused_wgrad(
+    const msha_graph* g, int32_t heads, int32_t feat, int32_t dtype, const float* el,
+    const float* er, const void* hc, const float* lse, const void* u, const void* u_lo,
+    const void* dU, float neg_slope, float drop_p, uint64_t seed, uint64_t offset,
+    const float* uc, const float* qc, float* d_el, float* d_er, void* d_hc, float* de, void* ws,
+    size_t ws_bytes, const void* X, int64_t ldx, int64_t K, const float* a_l, const float* a_r,
+    const int32_t* cut, int32_t nb, void* wg_ws, size_t wg_ws_bytes, msha_stream_t stream) {
+  if (int rc = check_graph(g, true)) return rc;
+  MSHA_ARG_CHECK(el && er && hc && lse && u && dU && d_el && d_er && d_hc && X && a_l && a_r && cut,
+                 "edge_attention_bwd_fused_wgrad: null pointer");
+  MSHA_ARG_CHECK(uc && qc, "edge_attention_bwd_fused_wgrad: needs the forward's row terms");
+  MSHA_ARG_CHECK(drop_p >= 0.f && drop_p <= 1.f, "edge_attention_bwd_fused_wgrad: p must be in [0,1]");
+  MSHA_ARG_CHECK(g->n_edges == 0 || g->csc_eid, "edge_attention_bwd_fused_wgrad: needs csc_eid");
+  const int want = fused_wgrad_blocks(g, heads, feat, dtype, K, ldx, true, true, X, a_l, a_r);
+  if (want == 0 || nb != want)
+    return fail(MSHA_ERR_UNSUPPORTED,
+                "edge_attention_bwd_fused_wgrad: not covered (ask ..._wgrad_route first)");
+  MSHA_ARG_CHECK(ws != nullptr &&
+                     ws_bytes >= msha_edge_attention_bwd_fused_workspace_size(g, heads, feat),
+                 "edge_attention_bwd_fused_wgrad: workspace too small");
+  MSHA_ARG_CHECK(wg_ws != nullptr &&
+                     wg_ws_bytes >= msha_edge_attention_bwd_fused_wgrad_workspace_size(nb),
+                 "edge_attention_bwd_fused_wgrad: slab workspace too small");
+  (void)u_lo;
+  (void)de;
+  float* rec = (float*)ws;
+  float* slab = (float*)wg_ws;
+  float* cpart = slab + (size_t)nb * 128 * 128;
+  hipStream_t s = (hipStream_t)stream;
+  const Dropout dp = make_dropout(drop_p, seed, offset, s);
+#define XQ(h, f)                                                                               \
+  if (heads == h && feat == f) {                                                               \
+    hipLaunchKernelGGL((bwd_row_stats_kernel<h, f, float, true>), wave_grid(g->n_rows / 8 + 1), \
+                       dim3(256), 0, s, g->n_rows, el, lse, (const float*)u,                   \
+                       (const float*)nullptr, (const float*)dU, rec, uc, qc, g->rowflag, d_el); \
+    if constexpr (f * sizeof(float) <= 64)                                                     \
+      hipLaunchKernelGGL((bwd_cols_wgrad_kernel<h, f>), dim3((unsigned)nb),                    \
+                         dim3(64 * kFwWaves), 0, s, cut, g->colptr, g->csc_row, g->csc_eid,    \
+                         g->n_edges, g->rowflag, g->n_rows, (const float*)rec, er,             \
+                         (const float*)hc, (const float*)dU, neg_slope, dp, false,             \
+                         (float*)nullptr, (float*)d_hc, d_er, (const float*)X, ldx, a_l, a_r,  \
+                         (const float*)d_el, slab, cpart);                                     \
+    else                                                                                       \
+      hipLaunchKernelGGL((bwd_cols_wgrad_q_kernel<h, f>), dim3((unsigned)nb),                  \
+                         dim3(64 * kFwWaves), 0, s, cut, g->colptr, g->csc_row, g->csc_eid,    \
+                         g->rowflag, g->n_rows, (const float*)rec, er, (const float*)hc,       \
+                         (const float*)dU, neg_slope, dp, (float*)d_hc, d_er, (const float*)X, \
+                         ldx, a_l, a_r, (const float*)d_el, slab, cpart);                      \
+  }
+  XQ(8, 16) XQ(4, 32) XQ(2, 64) XQ(1, 128)
+#undef XQ
+  return check_launch("edge_attention_bwd_fused_wgrad");
 }
 
 // ---------------------------------------------------- scores from the gathered row ---

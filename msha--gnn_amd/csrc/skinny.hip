@@ -2155,7 +2155,29 @@ int skinny_wgrad(int64_t M, int64_t N, int64_t K, const float* A, int64_t sAm, i
   return 1;
 }
 
+// The block-order sum alone: C = sum_b slab[b] and, with cpart, cs1 / cs2 from
+// cpart[which][n][b] -- for slabs that another kernel wrote in wgrad_kernel's layouts (the
+// column pass with the weight gradient inside, edge_attention.hip).
+void skinny_wgrad_reduce(const float* slab, int nb, float* C, int64_t ldc, const float* cpart,
+                         float* cs1, float* cs2, hipStream_t s) {
+  hipLaunchKernelGGL(sk::wgrad_reduce_kernel<float>,
+                     dim3(128 * 128 / (4 * sk::kWrCols) + (cpart != nullptr ? 2 * 128 / 4 : 0)),
+                     dim3(256), 0, s, slab, nb, C, ldc, 0.f, cpart, cs1, cs2);
+}
+
 }  // namespace msha
+
+// (ABI 16, added) dW (128 x 128, pitch ldc), dal, dar (128 each) from the nb slabs and the
+// partials that msha_edge_attention_bwd_fused_wgrad left in ws
+extern "C" int msha_wgrad_reduce(const void* ws, int32_t nb, float* dW, int64_t ldc, float* dal,
+                                 float* dar, msha_stream_t stream) {
+  MSHA_ARG_CHECK(ws && dW && dal && dar, "wgrad_reduce: null pointer");
+  MSHA_ARG_CHECK(nb > 0 && nb <= 256 && ldc >= 128, "wgrad_reduce: bad sizes");
+  const float* slab = (const float*)ws;
+  msha::skinny_wgrad_reduce(slab, nb, dW, ldc, slab + (size_t)nb * 128 * 128, dal, dar,
+                            (hipStream_t)stream);
+  return msha::check_launch("wgrad_reduce");
+}
 
 // Diagnostic: install (buf != NULL) or remove the per-wave timeline buffer of the skinny
 // kernels (slots x 64 uint64 words, device memory); MSHA_ERR_UNSUPPORTED unless the library

@@ -145,10 +145,47 @@ def _memo(obj, key, make):
     return v
 
 
+class _ProjTag:
+    """What project_scores leaves on its output h (``h._msha_proj``) for a square graph's
+    edge_attention backward: the projection's input and score vectors, so the column pass
+    can add the weight gradient's X^T D' for its own columns
+    (msha_edge_attention_bwd_fused_wgrad), and ``record``: what that pass left for
+    _ProjectScores.backward (the slab workspace, the block count and the identity of the
+    gradient tensors the slabs were computed from)."""
+
+    __slots__ = ("X", "al", "ar", "record")
+
+    def __init__(self, X, al, ar):
+        self.X, self.al, self.ar, self.record = X, al, ar, None
+
+    def take(self):
+        """The record, once: it holds the slab workspace and the gradient tensors."""
+        rec, self.record = self.record, None
+        return rec
+
+
+# how often the column pass carried the weight gradient / the reduce ran alone (tests)
+WGRAD_FUSED_CALLS = {"cols": 0, "reduce": 0}
+
+
+def _same(t, ident):
+    """``t`` is the tensor (or a view of the whole of it) whose (data_ptr, _version) is ident."""
+    return t is not None and (t.data_ptr(), t._version) == ident
+
+
 class _EdgeAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, el, er, hc, hs, graph: Graph, p: float, seed: int, slope: float, ar=None):
         n, H = el.shape
+        # hc is (a view of the whole of) a projection's own output: its tag
+        base = hc._base if hc._base is not None else hc
+        tag = getattr(base, "_msha_proj", None)
+        if tag is not None and not (base.dim() == 2 and base.is_contiguous()
+                                    and hc.is_contiguous() and base.data_ptr() == hc.data_ptr()
+                                    and base.numel() == hc.numel()
+                                    and base.shape[0] == hc.shape[0]):
+            tag = None
+        ctx.proj_tag = tag
         m, H2, F = hc.shape
         assert H2 == H and m == graph.n_cols and n == graph.n_rows
         dt = _table_dtype(hc, hs)
@@ -350,6 +387,34 @@ def _bwd_fused(ctx, el, er, hc, lse, u, u_lo, dU, d_el, hs, rowterms=(), ar=None
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     d_hc = torch.empty(m, H, F, device=dev, dtype=hc.dtype)
     d_er = torch.empty(m, H, device=dev, dtype=torch.float32)
+    tag = getattr(ctx, "proj_tag", None)
+    if tag is not None:
+        tag.record = None
+    nb = 0
+    if (tag is not None and uc is not None and ar is None and hc.dtype == torch.float32
+            and not ctx.has_hs and tag.X.shape[0] == m == n and tag.X.stride(1) == 1):
+        # square graph over the projection's own rows: the column pass carries the weight
+        # gradient where the library covers the call (host-only query)
+        nb = int(_lib.fn("msha_edge_attention_bwd_fused_wgrad_route")(
+            g, H, F, _code(hc.dtype), tag.X.shape[1], tag.X.stride(0), 1, 1, tag.X.data_ptr(),
+            tag.al.data_ptr(), tag.ar.data_ptr()))
+    if nb > 0:
+        cut = graph.col_ranges(nb)
+        wgb = int(_lib.fn("msha_edge_attention_bwd_fused_wgrad_workspace_size")(nb))
+        wg = torch.empty(wgb, dtype=torch.uint8, device=dev)
+        ev = _timed("edge_attention_bwd_fused")
+        _lib.call("msha_edge_attention_bwd_fused_wgrad", g, H, F, _code(hc.dtype), el.data_ptr(),
+                  er.data_ptr(), hc.data_ptr(), lse.data_ptr(), u.data_ptr(), None, dU.data_ptr(),
+                  ctx.slope, ctx.p, ctx.seed, 0, uc.data_ptr(), qc.data_ptr(), d_el.data_ptr(),
+                  d_er.data_ptr(), d_hc.data_ptr(), None, ws.data_ptr(), wsb, tag.X.data_ptr(),
+                  tag.X.stride(0), tag.X.shape[1], tag.al.data_ptr(), tag.ar.data_ptr(),
+                  cut.data_ptr(), nb, wg.data_ptr(), wgb, s)
+        if ev is not None:
+            ev[1].record()
+        WGRAD_FUSED_CALLS["cols"] += 1
+        # the slabs hold X^T (d_hc + d_el (x) al + d_er (x) ar) of exactly these tensors
+        tag.record = (wg, nb, tuple((t, (t.data_ptr(), t._version)) for t in (d_hc, d_el, d_er)))
+        return d_el, d_er, d_hc, None, None, None, None, None, None
     ev = _timed("edge_attention_bwd_fused")
     _lib.call("msha_edge_attention_bwd_fused_rs" if ar is not None else
               "msha_edge_attention_bwd_fused_ex", g, H, F, _code(hc.dtype), el.data_ptr(),
@@ -621,6 +686,12 @@ class _ProjectScores(torch.autograd.Function):
                   h.data_ptr(), _lib.ptr(el), _lib.ptr(er), _stream(X))
         ctx.heads, ctx.feat = heads, feat
         ctx.save_for_backward(X, W, al, ar, h)
+        ctx.proj_tag = None
+        # only where the backward would use the slabs (W, al, ar all want gradients): a frozen
+        # W would leave the column pass's extra work and its record unused
+        if (dt == torch.float32 and al is not None and ar is not None and not ctx.small
+                and all(ctx.needs_input_grad[1:4])):
+            ctx.proj_tag = h._msha_proj = _ProjTag(X, al, ar)
         outs = [h]
         if el is not None:
             outs.append(el)
@@ -640,6 +711,8 @@ class _ProjectScores(torch.autograd.Function):
         it = iter(dscores)
         d_el = next(it) if al is not None else None
         d_er = next(it) if ar is not None else None
+        tag = ctx.proj_tag
+        rec, dh_in = (None, None) if tag is None else (tag.take(), dh)
         if ctx.small:
             d_el, d_er = _f32c(d_el), _f32c(d_er)
             dh = None if dh is None else _tc(dh, dt)
@@ -669,6 +742,21 @@ class _ProjectScores(torch.autograd.Function):
                 dX = gemm_head_outer(dh, W.t(), 0, outer, **kw)
             if ctx.needs_input_grad[1]:
                 kw["out_dtype"] = wdt if dt == BF16 else None
+                if (rec is not None and ctx.needs_input_grad[2] and ctx.needs_input_grad[3]
+                        and d_el is not None and d_er is not None
+                        and all(_same(t, ident) for t, (_, ident) in
+                                zip((dh_in, d_el, d_er), rec[2]))):
+                    # the column pass left X^T D' of these very gradients as block slabs
+                    # (msha_edge_attention_bwd_fused_wgrad): only the block-order sum is left
+                    wg, nb, _ = rec
+                    dW = torch.empty(X.shape[1], H * Fd, device=dev, dtype=torch.float32)
+                    o1 = torch.empty(H, Fd, device=dev, dtype=torch.float32)
+                    o2 = torch.empty(H, Fd, device=dev, dtype=torch.float32)
+                    _lib.call("msha_wgrad_reduce", wg.data_ptr(), nb, dW.data_ptr(), dW.stride(0),
+                              o1.data_ptr(), o2.data_ptr(), s)
+                    WGRAD_FUSED_CALLS["reduce"] += 1
+                    dal, dar = _score_grads(d_el, d_er, o1, o2, al, ar, aldt, ardt)
+                    return dX, dW, dal, dar, None, None
                 if dt == torch.float32 and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3]):
                     # dW, dal, dar in one pass over the rows where the shape allows
                     fused = _wgrad_colsum(X, dh, outer, h, W)

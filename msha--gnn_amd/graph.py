@@ -52,6 +52,7 @@ class Graph:
 
     # -- CSC work plan: >= 1 chunk per column, long columns split into CSC_CHUNK slots
     def _build_plan(self, colptr):
+        self._colptr_host = np.ascontiguousarray(colptr, np.int64)
         cnt = np.diff(colptr)
         nch = np.maximum(1, (cnt + self._chunk - 1) // self._chunk)
         first = np.concatenate([[0], np.cumsum(nch)[:-1]])
@@ -66,6 +67,23 @@ class Graph:
                           chunk_end=t(end), n_multi=len(multi), multi_col=t(multi),
                           multi_first=t(first[multi]), multi_count=t(nch[multi]),
                           max_col=int(cnt.max()) if len(cnt) else 0)
+        # the column ranges of the column pass that carries the weight gradient, for the
+        # block count its route answers with (nothing is built inside a backward or a capture)
+        if self.n_cols > 0 and self.n_cols == self.n_rows:
+            self.col_ranges(int(_lib.fn("msha_col_range_blocks")(self.n_cols)))
+
+    def col_ranges(self, nb: int) -> torch.Tensor:
+        """cut[0..nb] (int32, device): contiguous column ranges of equal CSC slot counts for
+        the nb blocks of the column pass that carries the weight gradient
+        (msha_col_ranges).  A function of the graph and nb only; cached like the chunk plan."""
+        cache = self._plan.setdefault("col_ranges", {})
+        t = cache.get(nb)
+        if t is None:
+            cut = np.empty(nb + 1, np.int32)
+            _lib.call("msha_col_ranges", self._colptr_host.ctypes.data, self.n_cols, nb,
+                      cut.ctypes.data)
+            t = cache[nb] = torch.as_tensor(cut, device=self.device)
+        return t
 
     @property
     def desc(self) -> _lib.MshaGraph:
