@@ -273,6 +273,18 @@ MSHA_API int msha_bip_attention_bwd(const msha_graph* g, int32_t heads, int32_t 
  * CSR-walk backward; default 131072, or MSHA_BIP2_BWD_MIN_ROWS): rows >= 0 sets it for
  * the process and returns the previous value, rows < 0 only returns it. */
 MSHA_API int64_t msha_bip2_bwd_min_rows(int64_t rows);
+/* (ABI 16, added: a new symbol only, MSHA_ABI_VERSION stays 16) Host-only query: which
+ * kernel family msha_bip_attention_fwd (called with / without u_lo) and _bwd run for these
+ * arguments under the process's knobs (MSHA_BIP2, MSHA_BIP3, MSHA_BIP3_BWD32, the row count
+ * above), as fwd + 16 * bwd with MSHA_BIP_* below; 0 = not covered (msha_bip_supported is
+ * 0).  The launches ask the same function (csrc/bip_route.h).  Reads g's sizes and whether
+ * rowmask is set, no device memory; nothing is launched. */
+#define MSHA_BIP_NONE 0
+#define MSHA_BIP_WALK 1 /* CSR walk */
+#define MSHA_BIP_MASK 2 /* row masks */
+#define MSHA_BIP_MFMA 3 /* row masks on the matrix cores */
+MSHA_API int32_t msha_bip_route(const msha_graph* g, int32_t heads, int32_t feat, int32_t dtype,
+                                float neg_slope, float drop_p, int32_t has_u_lo);
 /* (ABI 15) The Ours intra forward's dropout draws: mode 1 packs the matched (batch entry,
  * node) pairs of consecutive nodes into one Philox draw per <= 64 pairs (default), mode 0
  * draws per node for the whole batch (MSHA_OURS_PACK_DRAWS=0 starts with it); both give

@@ -19,6 +19,8 @@ MSHA_OK, MSHA_ERR_ARG, MSHA_ERR_UNSUPPORTED, MSHA_ERR_HIP = 0, -1, -2, -3
 GEMM_LOADER_SCALAR, GEMM_LOADER_BNF, GEMM_LOADER_AK, GEMM_LOADER_VEC = 0, 1, 2, 4
 # MSHA_ROUTE_* (msha_project_scores_route, msha_pair_linear(_bf16)_route, ..._head_outer_route)
 ROUTE_TILED, ROUTE_RESIDENT, ROUTE_SPLIT = 0, 1, 2
+# MSHA_BIP_* (msha_bip_route: fwd + 16 * bwd)
+BIP_NONE, BIP_WALK, BIP_MASK, BIP_MFMA = 0, 1, 2, 3
 
 
 class MshaLibraryError(RuntimeError):
@@ -194,6 +196,7 @@ SIGNATURES = {
     "msha_pair_inner_fwd_ex": (C.c_int, [I64, I32, I32, P, I64, P, I64, P, I64, P, I64, P, P,
                                          P]),
     "msha_bip2_bwd_min_rows": (I64, [I64]),
+    "msha_bip_route": (I32, [GP, I32, I32, I32, F32, F32, I32]),
     "msha_pair_index_check": (C.c_int, [I64, P, I64, P, I64, P, P]),
     "msha_pair_linear_bf16": (C.c_int, [I64, I64, I64, P, I64, P, P, I64, P, P, P, I32, F32, U64,
                                         U64, P, P]),

@@ -56,10 +56,19 @@ __device__ __forceinline__ void bip_reduce_block(const BipReduce& r, int blk_id,
   }
 }
 
-// The host side (edge_bip.hip): launch the reduce now, or -- between
+// forward: partials [block][column][H F] -> v
+inline BipReduce bip_reduce_v(const float* part, int32_t nb, int32_t MD, void* v, bool bf16) {
+  return BipReduce{part, v, nullptr, nb, MD, MD, MD, 1, bf16 ? 1 : 0};
+}
+// backward: partials [block][d_hc (M D)][d_er (M H)], a block's record padded to 4 floats
+inline BipReduce bip_reduce_grads(const float* part, int32_t nb, int32_t MD, int32_t MH,
+                                  void* d_hc, float* d_er, bool bf16) {
+  return BipReduce{part, d_hc, d_er, nb, (MD + MH + 3) & ~3, MD + MH, MD, MH, bf16 ? 1 : 0};
+}
+
+// The host side (edge_bip.hip).  submit: launch the reduce now, or -- between
 // msha_bip_defer_reduce(1) and the next Ours-layer launch that takes it -- hand it over.
-// Returns true when deferred.
-bool bip_reduce_submit(const BipReduce& r, hipStream_t s);
+void bip_reduce_submit(const BipReduce& r, hipStream_t s);
 // the pending reduce of this host thread, removed: true when there was one submitted on
 // stream s (one submitted on another stream is launched there instead, false)
 bool bip_reduce_take(BipReduce& r, hipStream_t s);

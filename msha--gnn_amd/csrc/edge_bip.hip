@@ -31,13 +31,13 @@
 // u = att @ h1, v = att.T @ h2), Ours.py:84-86 (the backward's row coefficients).
 #include <atomic>
 
-#include "bip_reduce.h"
+#include "bip.h"
 #include "edge_geo.h"
 
 namespace msha {
 namespace bip {
 
-constexpr int kMaxMD = 4096;  // floats of one (M, H*F) LDS table: M = 32 at H*F = 128
+constexpr int kMaxMD = bip_route::kMaxMD;  // floats of one (M, H*F) LDS table
 constexpr int kWavesF = 8;    // fwd: 16 KB table + 8 x (16 KB v slab + 1.1 KB) = 153 KB
 constexpr int kWavesB = 7;    // bwd: two 16 KB tables + 7 x (d_hc slab + 1.6 KB) = 153 KB
 
@@ -817,34 +817,28 @@ thread_local BipReduce t_pending;
 thread_local hipStream_t t_pending_s = nullptr;
 }  // namespace
 
-static void bip_reduce_launch(const BipReduce& r, hipStream_t s) {
+void bip_reduce_run(const BipReduce& r, hipStream_t s) {
   if (r.bf16)
     hipLaunchKernelGGL(bip::bip_reduce_kernel<bf16_t>, dim3(r.blocks()), dim3(1024), 0, s, r);
   else
     hipLaunchKernelGGL(bip::bip_reduce_kernel<float>, dim3(r.blocks()), dim3(1024), 0, s, r);
 }
 
-void bip_reduce_run(const BipReduce& r, hipStream_t s) { bip_reduce_launch(r, s); }
-
-bool bip_reduce_submit(const BipReduce& r, hipStream_t s) {
+void bip_reduce_submit(const BipReduce& r, hipStream_t s) {
   if (t_has) {  // (one at a time: an earlier one not taken runs now)
-    bip_reduce_launch(t_pending, t_pending_s);
+    bip_reduce_run(t_pending, t_pending_s);
     t_has = false;
   }
-  if (!t_defer) {
-    bip_reduce_launch(r, s);
-    return false;
-  }
+  if (!t_defer) return bip_reduce_run(r, s);
   t_pending = r;
   t_pending_s = s;
   t_has = true;
-  return true;
 }
 
 bool bip_reduce_take(BipReduce& r, hipStream_t s) {
   if (!t_has) return false;
   if (t_pending_s != s) {  // another stream: not fused, run it where it was submitted
-    bip_reduce_launch(t_pending, t_pending_s);
+    bip_reduce_run(t_pending, t_pending_s);
     t_has = false;
     return false;
   }
@@ -852,29 +846,6 @@ bool bip_reduce_take(BipReduce& r, hipStream_t s) {
   t_has = false;
   return true;
 }
-
-// (edge_bip2.hip, edge_bip3.hip) block partials -> v or d_hc + d_er
-int bip_reduce(const float* part, int32_t nb, int32_t stride, int32_t n, int32_t n_t, void* out_t,
-               bool bf16, float* out_f, int32_t fblk, hipStream_t s) {
-  BipReduce r{part, out_t, out_f, nb, stride, n, n_t, fblk, bf16 ? 1 : 0};
-  bip_reduce_submit(r, s);
-  return 1;
-}
-bool bip2_ok(const msha_graph* g, int heads, int feat, float slope);
-int bip2_bwd(const msha_graph* g, int dtype, const float* el, const float* er, const void* hc,
-             const float* lse, const void* dU, const void* hs, const void* dV,
-             const float* row_coef, float slope, const Dropout& dp, float* d_el, float* d_er,
-             void* d_hc, void* d_hs, float* part, int nb, hipStream_t s);
-int bip2_fwd(const msha_graph* g, int dtype, const float* el, const float* er, const void* hc,
-             const void* hs, float slope, const Dropout& dp, void* u, float* lse, float* attd,
-             void* v, float* part, int nb, hipStream_t s);
-int bip3_bwd(const msha_graph* g, int dtype, const float* el, const float* er, const void* hc,
-             const float* lse, const void* dU, const void* hs, const void* dV,
-             const float* row_coef, float slope, const Dropout& dp, float* d_el, float* d_er,
-             void* d_hc, void* d_hs, float* part, int nb, hipStream_t s);
-int bip3_fwd(const msha_graph* g, int dtype, const float* el, const float* er, const void* hc,
-             const void* hs, float slope, const Dropout& dp, void* u, float* lse, float* attd,
-             void* v, float* part, int nb, hipStream_t s);
 
 namespace bip {
 
@@ -893,13 +864,26 @@ static int cu_count() {
 
 }  // namespace bip
 
-static bool bip_shape(int64_t n_cols, int heads, int feat) {
-  const int64_t D = (int64_t)heads * feat;
-  if (D % 64 != 0 || D > 256 || 64 % heads != 0) return false;
-  if (feat % (D / 64) != 0) return false;
-  // M <= 32 and M * H <= 64: a row's (edge, head) slots fit one 64-lane sub-group and a
-  // group's kPD rows fit the kColPages column pages
-  return n_cols <= 32 && n_cols * D <= bip::kMaxMD && n_cols * heads <= 64;
+static std::atomic<int64_t>& bip2_bwd_cut() {
+  static std::atomic<int64_t> cut{env_int("MSHA_BIP2_BWD_MIN_ROWS", 131072)};
+  return cut;
+}
+
+// The route of a call (bip_route.h) under this process's knobs: MSHA_BIP2 and MSHA_BIP3 read
+// once, MSHA_BIP3_BWD32 per call, the cut as msha_bip2_bwd_min_rows left it.  Reads the
+// graph's scalar fields and the null-ness of rowmask only.
+static bip_route::Route bip_route_of(const msha_graph* g, int heads, int feat, int dtype,
+                                     float slope, bool dropout, bool u_lo) {
+  if (g == nullptr) return {bip_route::kNone, bip_route::kNone};
+  static const int64_t bip2 = env_int("MSHA_BIP2", 1), bip3 = env_int("MSHA_BIP3", 1);
+  bool compiled = false;
+#define X(h, f) if (heads == h && feat == f) compiled = true;
+  MSHA_FOR_EACH_SHAPE(X)
+#undef X
+  const int esize = dtype == MSHA_DTYPE_F32 ? 4 : dtype == MSHA_DTYPE_BF16 ? 2 : 0;
+  const bip_route::Call c{g->n_rows, g->n_cols, g->n_edges, g->rowmask != nullptr, heads, feat,
+                          esize, compiled, slope, dropout, u_lo};
+  return bip_route::route(c, {bip2, bip3, (int)env_int("MSHA_BIP3_BWD32", -1), bip2_bwd_cut().load()});
 }
 
 }  // namespace msha
@@ -908,18 +892,15 @@ using namespace msha;
 
 extern "C" int msha_bip_supported(const msha_graph* g, int32_t heads, int32_t feat,
                                   int32_t dtype) {
-  // 32-bit buffer offsets below the kOOB mask bit: every table < 2 GiB
-  if (g == nullptr || g->n_rows <= 0 || g->n_cols <= 0 ||
-      g->n_rows * (int64_t)heads * feat * 4 >= ((int64_t)1 << 31) ||
-      g->n_edges * (int64_t)heads * 4 >= ((int64_t)1 << 31))
-    return 0;
-  if (dtype != MSHA_DTYPE_F32 && dtype != MSHA_DTYPE_BF16) return 0;
-  if (!bip_shape(g->n_cols, heads, feat)) return 0;
-  bool ok = false;
-#define X(h, f) if (heads == h && feat == f) ok = true;
-  MSHA_FOR_EACH_SHAPE(X)
-#undef X
-  return ok ? 1 : 0;
+  return bip_route_of(g, heads, feat, dtype, 0.f, false, false).fwd != bip_route::kNone;
+}
+
+// host-only: which kernel family msha_bip_attention_fwd / _bwd run for these arguments,
+// fwd + 16 * bwd (0 not covered, 1 CSR walk, 2 mask, 3 MFMA); nothing is launched
+extern "C" int32_t msha_bip_route(const msha_graph* g, int32_t heads, int32_t feat, int32_t dtype,
+                                  float neg_slope, float drop_p, int32_t has_u_lo) {
+  const bip_route::Route r = bip_route_of(g, heads, feat, dtype, neg_slope, drop_p > 0.f, has_u_lo != 0);
+  return r.fwd + 16 * r.bwd;
 }
 
 extern "C" size_t msha_bip_workspace_size(const msha_graph* g, int32_t heads, int32_t feat) {
@@ -928,50 +909,58 @@ extern "C" size_t msha_bip_workspace_size(const msha_graph* g, int32_t heads, in
   return (size_t)bip::cu_count() * rec * sizeof(float) + 256;
 }
 
-template <int H, int F, typename T>
-static void bip_launch_fwd(const msha_graph* g, const float* el, const float* er, const void* hc,
-                           const void* hs, float slope, const Dropout& dp, void* u, void* u_lo,
-                           float* lse, float* attd, void* v, float* part, int nb, hipStream_t s) {
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(bip::kWavesF * 64), 0, s, g->rowptr, g->col,
-                       g->rowflag, (int32_t)g->n_rows, (int32_t)g->n_cols, (int32_t)g->n_edges,
-                       el, er, (const T*)hc, (const T*)hs, slope, dp, (T*)u, (T*)u_lo, lse, attd,
-                       part);
-  };
-  if (hs != nullptr) {
-    if (attd != nullptr) go(bip::bip_fwd_kernel<H, F, T, true, true>);
-    else go(bip::bip_fwd_kernel<H, F, T, true, false>);
-    const int32_t MD = (int32_t)(g->n_cols * H * F);
-    // partials [block][column][H F]
-    const BipReduce r{part, v, nullptr, nb, MD, MD, MD, 1, sizeof(T) == 2 ? 1 : 0};
-    bip_reduce_submit(r, s);
-  } else if (attd != nullptr) go(bip::bip_fwd_kernel<H, F, T, false, true>);
-  else go(bip::bip_fwd_kernel<H, F, T, false, false>);
+// f(H, F) as integral constants for the walk's compiled (heads, feat); false: none matches
+template <class Fn>
+static bool bip_walk_shape(int heads, int feat, Fn&& f) {
+#define X(h, f_)                                                                          \
+  if (heads == h && feat == f_) {                                                         \
+    if constexpr ((h * f_) % 64 == 0 && h * f_ <= 256) {                                  \
+      f(std::integral_constant<int, h>{}, std::integral_constant<int, f_>{});             \
+      return true;                                                                        \
+    }                                                                                     \
+  }
+  MSHA_FOR_EACH_SHAPE(X)
+#undef X
+  return false;
 }
 
-template <int H, int F, typename T>
-static void bip_launch_bwd(const msha_graph* g, const float* el, const float* er, const void* hc,
-                           const float* lse, const void* dU, const void* hs, const void* dV,
-                           const float* row_coef, float slope, const Dropout& dp, float* d_el,
-                           float* d_er, void* d_hc, void* d_hs, float* part, int nb,
-                           hipStream_t s) {
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(bip::kWavesB * 64), 0, s, g->rowptr, g->col,
-                       g->rowflag, (int32_t)g->n_rows, (int32_t)g->n_cols, (int32_t)g->n_edges,
-                       el, er, (const T*)hc,
-                       lse, (const T*)dU, (const T*)hs, (const T*)dV, row_coef, slope, dp, d_el,
-                       (T*)d_hs, part);
-  };
-  const bool hsb = dV != nullptr, cf = row_coef != nullptr;
-  if (hsb && cf) go(bip::bip_bwd_kernel<H, F, T, true, true>);
-  else if (hsb) go(bip::bip_bwd_kernel<H, F, T, true, false>);
-  else if (cf) go(bip::bip_bwd_kernel<H, F, T, false, true>);
-  else go(bip::bip_bwd_kernel<H, F, T, false, false>);
-  const int32_t MD = (int32_t)(g->n_cols * H * F), MH = (int32_t)(g->n_cols * H);
-  // partials [block][d_hc (M D)][d_er (M H)]
-  const BipReduce r{part, d_hc, d_er, nb, bip::part_stride(MD + MH), MD + MH, MD, MH,
-                    sizeof(T) == 2 ? 1 : 0};
-  bip_reduce_submit(r, s);
+// the CSR walk: only this family writes u_lo (bf16 tables)
+static bool bip_walk_fwd(const BipFwd& a, int heads, int feat, hipStream_t s) {
+  const msha_graph* g = a.g;
+  return bip_walk_shape(heads, feat, [&](auto H, auto F) {
+    with_bools(
+        [&](auto BF, auto HS, auto A) {
+          using T = bip_table_t<decltype(BF)::value>;
+          hipLaunchKernelGGL(
+              (bip::bip_fwd_kernel<H(), F(), T, decltype(HS)::value, decltype(A)::value>),
+              dim3(a.nb), dim3(bip::kWavesF * 64), 0, s, g->rowptr, g->col, g->rowflag,
+              (int32_t)g->n_rows, (int32_t)g->n_cols, (int32_t)g->n_edges, a.el, a.er,
+              (const T*)a.hc, (const T*)a.hs, a.slope, a.dp, (T*)a.u,
+              (T*)(sizeof(T) == 2 ? a.u_lo : nullptr), a.lse, a.attd, a.part);
+        },
+        a.bf16(), a.hs != nullptr, a.attd != nullptr);
+    if (a.hs != nullptr)
+      bip_reduce_submit(bip_reduce_v(a.part, a.nb, (int32_t)(g->n_cols * H() * F()), a.v, a.bf16()), s);
+  });
+}
+
+static bool bip_walk_bwd(const BipBwd& a, int heads, int feat, hipStream_t s) {
+  const msha_graph* g = a.g;
+  return bip_walk_shape(heads, feat, [&](auto H, auto F) {
+    with_bools(
+        [&](auto BF, auto HS, auto C) {
+          using T = bip_table_t<decltype(BF)::value>;
+          hipLaunchKernelGGL(
+              (bip::bip_bwd_kernel<H(), F(), T, decltype(HS)::value, decltype(C)::value>),
+              dim3(a.nb), dim3(bip::kWavesB * 64), 0, s, g->rowptr, g->col, g->rowflag,
+              (int32_t)g->n_rows, (int32_t)g->n_cols, (int32_t)g->n_edges, a.el, a.er,
+              (const T*)a.hc, a.lse, (const T*)a.dU, (const T*)a.hs, (const T*)a.dV, a.row_coef,
+              a.slope, a.dp, a.d_el, (T*)a.d_hs, a.part);
+        },
+        a.bf16(), a.dV != nullptr, a.row_coef != nullptr);
+    bip_reduce_submit(bip_reduce_grads(a.part, a.nb, (int32_t)(g->n_cols * H() * F()),
+                                       (int32_t)(g->n_cols * H()), a.d_hc, a.d_er, a.bf16()), s);
+  });
 }
 
 extern "C" int msha_bip_attention_fwd(const msha_graph* g, int32_t heads, int32_t feat,
@@ -985,43 +974,20 @@ extern "C" int msha_bip_attention_fwd(const msha_graph* g, int32_t heads, int32_
   MSHA_ARG_CHECK(el && er && hc && u && lse, "bip_attention_fwd: null pointer");
   MSHA_ARG_CHECK((hs == nullptr) == (v == nullptr), "bip_attention_fwd: hs and v go together");
   MSHA_ARG_CHECK(drop_p >= 0.f && drop_p <= 1.f, "bip_attention_fwd: p must be in [0,1]");
-  if (!msha_bip_supported(g, heads, feat, dtype))
+  const int kind = bip_route_of(g, heads, feat, dtype, neg_slope, drop_p > 0.f, u_lo != nullptr).fwd;
+  if (kind == bip_route::kNone)
     return fail(MSHA_ERR_UNSUPPORTED, "bip_attention_fwd: graph/shape not covered (msha_bip_supported)");
-  const int nb = bip::cu_count();
   if (hs != nullptr)
     MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= msha_bip_workspace_size(g, heads, feat),
                    "bip_attention_fwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const Dropout dp = make_dropout(drop_p, seed, offset, s);
-  // the MFMA kernels (edge_bip3.hip) from msha_bip2_bwd_min_rows rows up; below it (the
-  // shipped graphs: < 1 tile per wave) the mask forward of edge_bip2.hip
-  if (u_lo == nullptr && bip2_ok(g, heads, feat, neg_slope) &&
-      ((g->n_rows >= msha_bip2_bwd_min_rows(-1) &&
-        bip3_fwd(g, dtype, el, er, hc, hs, neg_slope, dp, u, lse, attd, v, (float*)ws, nb, s)) ||
-       bip2_fwd(g, dtype, el, er, hc, hs, neg_slope, dp, u, lse, attd, v, (float*)ws, nb, s)))
-    return check_launch("bip_attention_fwd");
-  bool done = false;
-#define X(h, f)                                                                                  \
-  if (heads == h && feat == f) {                                                                 \
-    if constexpr ((h * f) % 64 == 0 && h * f <= 256) {                                           \
-      if (dtype == MSHA_DTYPE_BF16)                                                              \
-        bip_launch_fwd<h, f, bf16_t>(g, el, er, hc, hs, neg_slope, dp, u, u_lo, lse, attd, v,    \
-                                     (float*)ws, nb, s);                                         \
-      else                                                                                       \
-        bip_launch_fwd<h, f, float>(g, el, er, hc, hs, neg_slope, dp, u, nullptr, lse, attd, v,  \
-                                    (float*)ws, nb, s);                                          \
-      done = true;                                                                               \
-    }                                                                                            \
-  }
-  MSHA_FOR_EACH_SHAPE(X)
-#undef X
-  if (!done) return fail(MSHA_ERR_UNSUPPORTED, "bip_attention_fwd: unsupported (heads, feat)");
+  const BipFwd a{g, dtype, el, er, hc, hs, neg_slope, make_dropout(drop_p, seed, offset, s), u, u_lo,
+                 lse, attd, v, (float*)ws, bip::cu_count()};
+  if (kind == bip_route::kMfma) bip3_fwd(a, s);
+  else if (kind == bip_route::kMask) bip2_fwd(a, s);
+  else if (!bip_walk_fwd(a, heads, feat, s))
+    return fail(MSHA_ERR_UNSUPPORTED, "bip_attention_fwd: unsupported (heads, feat)");
   return check_launch("bip_attention_fwd");
-}
-
-static std::atomic<int64_t>& bip2_bwd_cut() {
-  static std::atomic<int64_t> cut{env_int("MSHA_BIP2_BWD_MIN_ROWS", 131072)};
-  return cut;
 }
 
 // (ABI 16) 1: the block-partial reduce of the next bipartite forward / backward is handed to
@@ -1031,7 +997,7 @@ static std::atomic<int64_t>& bip2_bwd_cut() {
 extern "C" int msha_bip_defer_reduce(int32_t on) {
   t_defer = on != 0;
   if (!t_defer && t_has) {
-    bip_reduce_launch(t_pending, t_pending_s);
+    bip_reduce_run(t_pending, t_pending_s);
     t_has = false;
     return check_launch("bip_defer_reduce");
   }
@@ -1057,40 +1023,23 @@ extern "C" int msha_bip_attention_bwd(const msha_graph* g, int32_t heads, int32_
   MSHA_ARG_CHECK(dV == nullptr || (hs != nullptr && d_hs != nullptr),
                  "bip_attention_bwd: dV needs hs and d_hs");
   MSHA_ARG_CHECK(drop_p >= 0.f && drop_p <= 1.f, "bip_attention_bwd: p must be in [0,1]");
-  if (!msha_bip_supported(g, heads, feat, dtype))
+  const int kind = bip_route_of(g, heads, feat, dtype, neg_slope, drop_p > 0.f, false).bwd;
+  if (kind == bip_route::kNone)
     return fail(MSHA_ERR_UNSUPPORTED, "bip_attention_bwd: graph/shape not covered (msha_bip_supported)");
   MSHA_ARG_CHECK(ws != nullptr && ws_bytes >= msha_bip_workspace_size(g, heads, feat),
                  "bip_attention_bwd: workspace too small");
-  const int nb = bip::cu_count();
   hipStream_t s = (hipStream_t)stream;
-  const Dropout dp = make_dropout(drop_p, seed, offset, s);
-  // the MFMA backward (edge_bip3.hip; mask backward edge_bip2.hip with MSHA_BIP3=0) wins on
-  // large graphs (bip1m fp32: CSR walk 450 us, mask 380-416, MFMA ~400; bf16 MFMA 204) but
-  // not on the shipped ones (R15: MFMA 36.1, mask 36.6, CSR walk 31.6 us; rows per wave too
-  // few to amortise the per-block setup and partial epilogue).  MSHA_BIP2_BWD_MIN_ROWS /
-  // msha_bip2_bwd_min_rows (per process: tests run small graphs through both) move the
-  // cut, for the forward's choice as well.
-  if (g->n_rows >= msha_bip2_bwd_min_rows(-1) && bip2_ok(g, heads, feat, neg_slope) &&
-      (bip3_bwd(g, dtype, el, er, hc, lse, dU, hs, dV, row_coef, neg_slope, dp, d_el, d_er, d_hc,
-                d_hs, (float*)ws, nb, s) ||
-       bip2_bwd(g, dtype, el, er, hc, lse, dU, hs, dV, row_coef, neg_slope, dp, d_el, d_er, d_hc,
-                d_hs, (float*)ws, nb, s)))
-    return check_launch("bip_attention_bwd");
-  bool done = false;
-#define X(h, f)                                                                                  \
-  if (heads == h && feat == f) {                                                                 \
-    if constexpr ((h * f) % 64 == 0 && h * f <= 256) {                                           \
-      if (dtype == MSHA_DTYPE_BF16)                                                              \
-        bip_launch_bwd<h, f, bf16_t>(g, el, er, hc, lse, dU, hs, dV, row_coef, neg_slope, dp,    \
-                                     d_el, d_er, d_hc, d_hs, (float*)ws, nb, s);                 \
-      else                                                                                       \
-        bip_launch_bwd<h, f, float>(g, el, er, hc, lse, dU, hs, dV, row_coef, neg_slope, dp,     \
-                                    d_el, d_er, d_hc, d_hs, (float*)ws, nb, s);                  \
-      done = true;                                                                               \
-    }                                                                                            \
-  }
-  MSHA_FOR_EACH_SHAPE(X)
-#undef X
-  if (!done) return fail(MSHA_ERR_UNSUPPORTED, "bip_attention_bwd: unsupported (heads, feat)");
+  const BipBwd a{g, dtype, el, er, hc, lse, dU, hs, dV, row_coef, neg_slope,
+                 make_dropout(drop_p, seed, offset, s), d_el, d_er, d_hc, d_hs, (float*)ws,
+                 bip::cu_count()};
+  // the MFMA backward (mask backward with MSHA_BIP3=0) wins on large graphs (bip1m fp32: CSR
+  // walk 450 us, mask 380-416, MFMA ~400; bf16 MFMA 204) but not on the shipped ones (R15:
+  // MFMA 36.1, mask 36.6, CSR walk 31.6 us; rows per wave too few to amortise the per-block
+  // setup and partial epilogue): hence the route's row cut, MSHA_BIP2_BWD_MIN_ROWS /
+  // msha_bip2_bwd_min_rows (per process: tests run small graphs through both)
+  if (kind == bip_route::kMfma) bip3_bwd(a, s);
+  else if (kind == bip_route::kMask) bip2_bwd(a, s);
+  else if (!bip_walk_bwd(a, heads, feat, s))
+    return fail(MSHA_ERR_UNSUPPORTED, "bip_attention_bwd: unsupported (heads, feat)");
   return check_launch("bip_attention_bwd");
 }

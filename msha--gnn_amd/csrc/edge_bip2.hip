@@ -20,14 +20,10 @@
 // Dropout draws the same Philox stream as every other edge kernel: element e * H + h of
 // CSR edge e.  Accumulation order: u over the row's edges in column order (= CSR order),
 // v over rows in wave order, waves in block order, blocks in order (bip_reduce).
+#include "bip.h"
 #include "edge_geo.h"
 
 namespace msha {
-
-// block partials -> output (edge_bip.hip bip_reduce_kernel): out[i] = sum_b part[b][i]
-int bip_reduce(const float* part, int32_t nb, int32_t stride, int32_t n, int32_t n_t, void* out_t,
-               bool bf16, float* out_f, int32_t fblk, hipStream_t s);
-
 namespace bip2 {
 
 typedef float f32x32 __attribute__((ext_vector_type(32)));
@@ -571,78 +567,37 @@ __global__ void __launch_bounds__(kWavesB * 64) bip2_bwd_kernel(
 
 }  // namespace bip2
 
-bool bip2_ok(const msha_graph* g, int heads, int feat, float slope) {
-  static const bool env = env_int("MSHA_BIP2", 1) != 0;
-  return env && heads == 2 && feat == 64 && g->rowmask != nullptr && g->n_cols <= 32 &&
-         slope >= 0.f && slope <= 1.f && g->n_rows * (int64_t)bip2::kD * 4 < (1ll << 31) &&
-         g->n_edges * 8ll < (1ll << 31);
+void bip2_fwd(const BipFwd& a, hipStream_t s) {
+  const msha_graph* g = a.g;
+  with_bools(
+      [&](auto BF, auto HS, auto A) {
+        using T = bip_table_t<decltype(BF)::value>;
+        hipLaunchKernelGGL((bip2::bip2_fwd_kernel<T, decltype(HS)::value, decltype(A)::value>),
+                           dim3(a.nb), dim3(bip2::kWaves * 64), 0, s, g->rowmask, g->rowptr,
+                           g->rowflag, (int32_t)g->n_rows, (int32_t)g->n_cols,
+                           (int32_t)g->n_edges, a.el, a.er, (const T*)a.hc, (const T*)a.hs,
+                           a.slope, a.dp, (T*)a.u, a.lse, a.attd, a.part);
+      },
+      a.bf16(), a.hs != nullptr, a.attd != nullptr);
+  if (a.hs != nullptr)
+    bip_reduce_submit(bip_reduce_v(a.part, a.nb, (int32_t)(g->n_cols * bip2::kD), a.v, a.bf16()), s);
 }
 
-// 1 = launched (forward + the v reduce), 0 = not covered
-int bip2_fwd(const msha_graph* g, int dtype, const float* el, const float* er, const void* hc,
-             const void* hs, float slope, const Dropout& dp, void* u, float* lse, float* attd,
-             void* v, float* part, int nb, hipStream_t s) {
-  const dim3 grid(nb), block(bip2::kWaves * 64);
-  auto go = [&](auto kern, auto tag) {
-    using T = decltype(tag);
-    hipLaunchKernelGGL(kern, grid, block, 0, s, g->rowmask, g->rowptr, g->rowflag,
-                       (int32_t)g->n_rows, (int32_t)g->n_cols, (int32_t)g->n_edges, el, er,
-                       (const T*)hc, (const T*)hs, slope, dp, (T*)u, lse, attd, part);
-  };
-  const bool bf = dtype == MSHA_DTYPE_BF16;
-  const bool H = hs != nullptr, A = attd != nullptr;
-#define GO(T_, HS_, A_) go(bip2::bip2_fwd_kernel<T_, HS_, A_>, T_{})
-  if (bf) {
-    if (H && A) GO(bf16_t, true, true);
-    else if (H) GO(bf16_t, true, false);
-    else if (A) GO(bf16_t, false, true);
-    else GO(bf16_t, false, false);
-  } else {
-    if (H && A) GO(float, true, true);
-    else if (H) GO(float, true, false);
-    else if (A) GO(float, false, true);
-    else GO(float, false, false);
-  }
-#undef GO
-  if (H) {
-    const int32_t MD = (int32_t)(g->n_cols * bip2::kD);
-    bip_reduce(part, nb, MD, MD, MD, v, bf, nullptr, 1, s);
-  }
-  return 1;
+void bip2_bwd(const BipBwd& a, hipStream_t s) {
+  const msha_graph* g = a.g;
+  with_bools(
+      [&](auto BF, auto HS, auto C, auto D) {
+        using T = bip_table_t<decltype(BF)::value>;
+        hipLaunchKernelGGL(
+            (bip2::bip2_bwd_kernel<T, decltype(HS)::value, decltype(C)::value, decltype(D)::value>),
+            dim3(a.nb), dim3(bip2::kWavesB * 64), 0, s, g->rowmask, g->rowptr, g->rowflag,
+            (int32_t)g->n_rows, (int32_t)g->n_cols, (int32_t)g->n_edges, a.el, a.er,
+            (const T*)a.hc, a.lse, (const T*)a.dU, (const T*)a.hs, (const T*)a.dV, a.row_coef,
+            a.slope, a.dp, a.d_el, (T*)a.d_hs, a.part);
+      },
+      a.bf16(), a.dV != nullptr, a.row_coef != nullptr, a.dp.active);
+  bip_reduce_submit(bip_reduce_grads(a.part, a.nb, (int32_t)(g->n_cols * bip2::kD),
+                                     (int32_t)(g->n_cols * 2), a.d_hc, a.d_er, a.bf16()), s);
 }
 
-}  // namespace msha
-
-namespace msha {
-int bip2_bwd(const msha_graph* g, int dtype, const float* el, const float* er, const void* hc,
-             const float* lse, const void* dU, const void* hs, const void* dV,
-             const float* row_coef, float slope, const Dropout& dp, float* d_el, float* d_er,
-             void* d_hc, void* d_hs, float* part, int nb, hipStream_t s) {
-  const dim3 grid(nb), block(bip2::kWavesB * 64);
-  auto go = [&](auto kern, auto tag) {
-    using T = decltype(tag);
-    hipLaunchKernelGGL(kern, grid, block, 0, s, g->rowmask, g->rowptr, g->rowflag,
-                       (int32_t)g->n_rows, (int32_t)g->n_cols, (int32_t)g->n_edges, el, er,
-                       (const T*)hc, lse, (const T*)dU, (const T*)hs, (const T*)dV, row_coef,
-                       slope, dp, d_el, (T*)d_hs, part);
-  };
-  const bool bf = dtype == MSHA_DTYPE_BF16;
-  const bool H = dV != nullptr, C = row_coef != nullptr, D = dp.active;
-#define GO(T_, H_, C_, D_) go(bip2::bip2_bwd_kernel<T_, H_, C_, D_>, T_{})
-#define GO4(T_)                                      \
-  if (H && C && D) GO(T_, true, true, true);         \
-  else if (H && C) GO(T_, true, true, false);        \
-  else if (H && D) GO(T_, true, false, true);        \
-  else if (H) GO(T_, true, false, false);            \
-  else if (C && D) GO(T_, false, true, true);        \
-  else if (C) GO(T_, false, true, false);            \
-  else if (D) GO(T_, false, false, true);            \
-  else GO(T_, false, false, false);
-  if (bf) { GO4(bf16_t) } else { GO4(float) }
-#undef GO4
-#undef GO
-  const int32_t MD = (int32_t)(g->n_cols * bip2::kD), MH = (int32_t)(g->n_cols * 2);
-  bip_reduce(part, nb, (MD + MH + 3) & ~3, MD + MH, MD, d_hc, bf, d_er, MH, s);
-  return 1;
-}
 }  // namespace msha

@@ -27,6 +27,7 @@
 // the stream of every other edge kernel: element e * 2 + h of CSR edge e.
 #include <algorithm>
 
+#include "bip.h"
 #include "edge_geo.h"
 
 // no fp contraction in this file: a product and a later add are not fused differently
@@ -35,10 +36,6 @@
 #pragma clang fp contract(off)
 
 namespace msha {
-
-int bip_reduce(const float* part, int32_t nb, int32_t stride, int32_t n, int32_t n_t, void* out_t,
-               bool bf16, float* out_f, int32_t fblk, hipStream_t s);
-
 namespace bip3 {
 
 // ---- per-wave timeline (diagnostic build, -DSK_TIMELINE; scripts/bip_timeline.py) ------
@@ -1137,94 +1134,49 @@ __global__ void __launch_bounds__(kWaves * 64) bip3_bwd_kernel(
 
 }  // namespace bip3
 
-bool bip3_enabled() {
-  static const bool env = env_int("MSHA_BIP3", 1) != 0;
-  return env;
-}
-
-// 1 = launched (forward + the v reduce); the caller checked bip2_ok (2 x 64, M <= 32,
-// row masks)
-int bip3_fwd(const msha_graph* g, int dtype, const float* el, const float* er, const void* hc,
-             const void* hs, float slope, const Dropout& dp, void* u, float* lse, float* attd,
-             void* v, float* part, int nb, hipStream_t s) {
-  if (!bip3_enabled()) return 0;
+void bip3_fwd(const BipFwd& a, hipStream_t s) {
+  const msha_graph* g = a.g;
   const int32_t n_tiles = (int32_t)((g->n_rows + bip3::kTile - 1) / bip3::kTile);
   // no more blocks than tiles' worth of waves (small graphs: every wave at least one tile)
-  const int nbk = (int)std::max<int64_t>(1, std::min<int64_t>(nb, (n_tiles + 3) / 4));  // 4 wave pairs a block
-  const dim3 grid(nbk), block(bip3::kWaves * 64);
-  auto go = [&](auto kern, auto tag) {
-    using T = decltype(tag);
-    hipLaunchKernelGGL(kern, grid, block, 0, s, g->rowmask, g->rowptr, g->rowflag,
-                       (int32_t)g->n_rows, (int32_t)g->n_cols, (int32_t)g->n_edges, el, er,
-                       (const T*)hc, (const T*)hs, slope, dp, (T*)u, lse, attd, part);
-  };
-  const bool bf = dtype == MSHA_DTYPE_BF16;
-  const bool H = hs != nullptr, A = attd != nullptr, D = dp.active;
-#define GO(T_, H_, A_, D_) go(bip3::bip3_fwd_kernel<T_, H_, A_, D_>, T_{})
-#define GO8(T_)                                 \
-  if (H && A && D) GO(T_, true, true, true);    \
-  else if (H && A) GO(T_, true, true, false);   \
-  else if (H && D) GO(T_, true, false, true);   \
-  else if (H) GO(T_, true, false, false);       \
-  else if (A && D) GO(T_, false, true, true);   \
-  else if (A) GO(T_, false, true, false);       \
-  else if (D) GO(T_, false, false, true);       \
-  else GO(T_, false, false, false);
-  if (bf) { GO8(bf16_t) } else { GO8(float) }
-#undef GO8
-#undef GO
-  if (H) {
-    const int32_t MD = (int32_t)(g->n_cols * bip3::kD);
-    bip_reduce(part, nbk, MD, MD, MD, v, bf, nullptr, 1, s);
-  }
-  return 1;
+  const int nbk = (int)std::max<int64_t>(1, std::min<int64_t>(a.nb, (n_tiles + 3) / 4));  // 4 wave pairs a block
+  with_bools(
+      [&](auto BF, auto HS, auto A, auto D) {
+        using T = bip_table_t<decltype(BF)::value>;
+        hipLaunchKernelGGL(
+            (bip3::bip3_fwd_kernel<T, decltype(HS)::value, decltype(A)::value, decltype(D)::value>),
+            dim3(nbk), dim3(bip3::kWaves * 64), 0, s, g->rowmask, g->rowptr, g->rowflag,
+            (int32_t)g->n_rows, (int32_t)g->n_cols, (int32_t)g->n_edges, a.el, a.er,
+            (const T*)a.hc, (const T*)a.hs, a.slope, a.dp, (T*)a.u, a.lse, a.attd, a.part);
+      },
+      a.bf16(), a.hs != nullptr, a.attd != nullptr, a.dp.active);
+  if (a.hs != nullptr)
+    bip_reduce_submit(bip_reduce_v(a.part, nbk, (int32_t)(g->n_cols * bip3::kD), a.v, a.bf16()), s);
 }
 
-// 1 = launched (backward + the d_hc / d_er reduce)
-int bip3_bwd(const msha_graph* g, int dtype, const float* el, const float* er, const void* hc,
-             const float* lse, const void* dU, const void* hs, const void* dV,
-             const float* row_coef, float slope, const Dropout& dp, float* d_el, float* d_er,
-             void* d_hc, void* d_hs, float* part, int nb, hipStream_t s) {
-  if (!bip3_enabled()) return 0;
-  // fp32: with the hs pieces loaded in their own tile (BIP3_HSSYNC) the loop no longer
-  // spills and this kernel beats the mask backward of edge_bip2.hip at bip1m (370-377 vs
-  // 393-400 us, profiles/round6_bwd32_ab; the spilled form's scratch reloads waited for every
-  // outstanding load).  Its dropout variants still spill (the keep words): with dropout the
-  // mask kernel runs.  MSHA_BIP3_BWD32 (read per call): 1 forces this kernel, 0 the mask one.
-  if (dtype != MSHA_DTYPE_BF16) {
-    const int force = (int)env_int("MSHA_BIP3_BWD32", -1);
-    if (force == 0 || (force < 0 && dp.active)) return 0;
-  }
+// fp32: with the hs pieces loaded in their own tile (BIP3_HSSYNC) the loop no longer spills
+// and this kernel beats the mask backward of edge_bip2.hip at bip1m (370-377 vs 393-400 us,
+// profiles/round6_bwd32_ab; the spilled form's scratch reloads waited for every outstanding
+// load).  Its dropout variants still spill (the keep words): with dropout the route
+// (bip_route.h) takes the mask kernel unless MSHA_BIP3_BWD32 forces this one.
+void bip3_bwd(const BipBwd& a, hipStream_t s) {
+  const msha_graph* g = a.g;
   const int32_t n_tiles = (int32_t)((g->n_rows + bip3::kTile - 1) / bip3::kTile);
   // blocks in head pairs (blockIdx.x & 1 = head), each wave at least one tile
-  const int64_t pairs = std::max<int64_t>(1, std::min<int64_t>(nb / 2, (n_tiles + bip3::kWaves - 1) / bip3::kWaves));
+  const int64_t pairs = std::max<int64_t>(1, std::min<int64_t>(a.nb / 2, (n_tiles + bip3::kWaves - 1) / bip3::kWaves));
   const int nbk = (int)(2 * pairs);
-  const dim3 grid(nbk), block(bip3::kWaves * 64);
-  auto go = [&](auto kern, auto tag) {
-    using T = decltype(tag);
-    hipLaunchKernelGGL(kern, grid, block, 0, s, g->rowmask, g->rowptr, g->rowflag,
-                       (int32_t)g->n_rows, (int32_t)g->n_cols, el, er, (const T*)hc, lse,
-                       (const T*)dU, (const T*)hs, (const T*)dV, row_coef, slope, dp, d_el,
-                       (T*)d_hs, part);
-  };
-  const bool bf = dtype == MSHA_DTYPE_BF16;
-  const bool H = dV != nullptr, C = row_coef != nullptr, D = dp.active;
-#define GO(T_, H_, C_, D_) go(bip3::bip3_bwd_kernel<T_, H_, C_, D_>, T_{})
-#define GO8(T_)                                 \
-  if (H && C && D) GO(T_, true, true, true);    \
-  else if (H && C) GO(T_, true, true, false);   \
-  else if (H && D) GO(T_, true, false, true);   \
-  else if (H) GO(T_, true, false, false);       \
-  else if (C && D) GO(T_, false, true, true);   \
-  else if (C) GO(T_, false, true, false);       \
-  else if (D) GO(T_, false, false, true);       \
-  else GO(T_, false, false, false);
-  if (bf) { GO8(bf16_t) } else { GO8(float) }
-#undef GO8
-#undef GO
-  const int32_t MD = (int32_t)(g->n_cols * bip3::kD), MH = (int32_t)(g->n_cols * 2);
-  bip_reduce(part, nbk, (MD + MH + 3) & ~3, MD + MH, MD, d_hc, bf, d_er, MH, s);
-  return 1;
+  with_bools(
+      [&](auto BF, auto HS, auto C, auto D) {
+        using T = bip_table_t<decltype(BF)::value>;
+        hipLaunchKernelGGL(
+            (bip3::bip3_bwd_kernel<T, decltype(HS)::value, decltype(C)::value, decltype(D)::value>),
+            dim3(nbk), dim3(bip3::kWaves * 64), 0, s, g->rowmask, g->rowptr, g->rowflag,
+            (int32_t)g->n_rows, (int32_t)g->n_cols, a.el, a.er, (const T*)a.hc, a.lse,
+            (const T*)a.dU, (const T*)a.hs, (const T*)a.dV, a.row_coef, a.slope, a.dp, a.d_el,
+            (T*)a.d_hs, a.part);
+      },
+      a.bf16(), a.dV != nullptr, a.row_coef != nullptr, a.dp.active);
+  bip_reduce_submit(bip_reduce_grads(a.part, nbk, (int32_t)(g->n_cols * bip3::kD),
+                                     (int32_t)(g->n_cols * 2), a.d_hc, a.d_er, a.bf16()), s);
 }
 
 }  // namespace msha

@@ -8,6 +8,8 @@
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import ctypes
 import functools
 import os
@@ -194,29 +196,26 @@ class _EdgeAttention(torch.autograd.Function):
         dev = el.device
         s = _stream(el)
         g = graph.desc
+        ctx.graph, ctx.p, ctx.seed, ctx.slope = graph, p, seed, slope
+        ctx.has_hs = hs is not None
         # (u-only with a_r keeps the row-score contract: er is then never read)
-        if (hs is not None or ar is None) and bip_ok(graph, H, F, dt):
-            # the repo's adjacency shape (M <= 32 recipients): msha_bip_attention_fwd,
-            # u and v in one pass over the rows (the column side stays in LDS)
-            u = torch.empty(n, H, F, device=dev, dtype=dt)
-            lse = torch.empty(n, H, device=dev, dtype=torch.float32)
-            v = torch.empty(m, H, F, device=dev, dtype=dt) if hs is not None else None
-            ws = _bip_ws(graph, H, F, dev)
-            ev = _timed("bip_attention_fwd")
-            _lib.call("msha_bip_attention_fwd", g, H, F, _code(dt), el.data_ptr(),
-                      er.data_ptr(), hc.data_ptr(), _lib.ptr(hs), slope, p, seed, 0,
-                      u.data_ptr(), None, lse.data_ptr(), None, _lib.ptr(v), ws.data_ptr(),
-                      ws.numel(), s)
-            if ev is not None:
-                ev[1].record()
-            ctx.graph, ctx.p, ctx.seed, ctx.slope = graph, p, seed, slope
-            ctx.has_hs, ctx.bip = hs is not None, True
-            ctx.save_for_backward(el, er, hc, hs if hs is not None else el.new_empty(0), lse)
-            return u if v is None else (u, v)
-        # scores from the gathered row (msha_edge_attention_fwd_rs): er_j = hc_j . a_r is
-        # recomputed from the row the kernel gathers anyway, in the forward and in the
-        # fused backward's column pass (the same bits in both); u-only path
-        rs = (ar is not None and hs is None and ROW_SCORES and FUSED_BWD
+        if hs is not None or (ar is None and bip_ok(graph, H, F, dt)):
+            # u and v: the bipartite kernels on the repo's adjacency shape (M <= 32
+            # recipients; u-only too), else the general forward + the CSC aggregate
+            it = _inter_fwd(graph, el, er, hc, hs, slope, p, seed,
+                            keep_u_lo=any(ctx.needs_input_grad[:4]), timed=True)
+            ctx.bip = it.bip
+            ctx.rowterms = ctx.rs = ctx.er_exact = False
+            empty = el.new_empty(0)
+            ctx.save_for_backward(el, er, hc, hs if hs is not None else empty, it.lse,
+                                  *(() if it.bip else
+                                    (it.u, it.u_lo if it.u_lo is not None else empty, empty)))
+            return it.u if it.v is None else (it.u, it.v)
+        # the general kernels, u-only.  Scores from the gathered row
+        # (msha_edge_attention_fwd_rs): er_j = hc_j . a_r is recomputed from the row the
+        # kernel gathers anyway, in the forward and in the fused backward's column pass (the
+        # same bits in both)
+        rs = (ar is not None and ROW_SCORES and FUSED_BWD
               and _lib.load().msha_edge_attention_row_scores_preferred(g, H, F, _code(dt)))
         # er from project_scores in the kernels' order is exactly what the forward
         # recomputes: the backward then reads er per column (no recompute from a_r)
@@ -227,85 +226,47 @@ class _EdgeAttention(torch.autograd.Function):
         # D = dU . u (include/msha_gnn.h, u_lo)
         u_lo = torch.empty_like(u) if dt == BF16 and any(ctx.needs_input_grad[:4]) else None
         lse = torch.empty(n, H, device=dev, dtype=torch.float32)
-        attd = None
-        if hs is not None:
-            attd = torch.empty(max(graph.n_edges, 1), H, device=dev, dtype=torch.float32)
-        # row terms for the u-only fused backward on large graphs (include/msha_gnn.h
+        # row terms for the fused backward on large graphs (include/msha_gnn.h
         # msha_edge_attention_fwd_ex): d_el without a per-edge de crossing CSC -> CSR
         uc = qc = None
-        if (hs is None and FUSED_BWD and ctx.needs_input_grad[0] and ROWTERMS
+        if (FUSED_BWD and ctx.needs_input_grad[0] and ROWTERMS
                 and _lib.load().msha_edge_attention_rowterms_preferred(g, H, F, _code(dt))):
             uc = torch.empty(n, H, F, device=dev, dtype=torch.float32)
             qc = torch.empty(n, H, device=dev, dtype=torch.float32)
-        ev = _timed("edge_attention_fwd")
-        if rs:
-            _lib.call("msha_edge_attention_fwd_rs", g, H, F, _code(dt), el.data_ptr(),
-                      ar.data_ptr(), hc.data_ptr(), slope, p, seed, 0, u.data_ptr(),
-                      _lib.ptr(u_lo), lse.data_ptr(), _lib.ptr(uc), _lib.ptr(qc), s)
-        else:
-            _lib.call("msha_edge_attention_fwd_ex", g, H, F, _code(dt), el.data_ptr(),
-                      er.data_ptr(), hc.data_ptr(), slope, p, seed, 0, u.data_ptr(),
-                      _lib.ptr(u_lo), lse.data_ptr(), _lib.ptr(attd), _lib.ptr(uc),
-                      _lib.ptr(qc), s)
-        if ev is not None:
-            ev[1].record()
-        v = None
-        if hs is not None:
-            v = torch.empty(m, H, F, device=dev, dtype=dt)
-            _csc_aggregate(graph, H, F, attd, None, hs, v, None, s)
-        ctx.graph, ctx.p, ctx.seed, ctx.slope = graph, p, seed, slope
-        ctx.has_hs, ctx.bip = hs is not None, False
+        with _events("edge_attention_fwd", True):
+            if rs:
+                _lib.call("msha_edge_attention_fwd_rs", g, H, F, _code(dt), el.data_ptr(),
+                          ar.data_ptr(), hc.data_ptr(), slope, p, seed, 0, u.data_ptr(),
+                          _lib.ptr(u_lo), lse.data_ptr(), _lib.ptr(uc), _lib.ptr(qc), s)
+            else:
+                _lib.call("msha_edge_attention_fwd_ex", g, H, F, _code(dt), el.data_ptr(),
+                          er.data_ptr(), hc.data_ptr(), slope, p, seed, 0, u.data_ptr(),
+                          _lib.ptr(u_lo), lse.data_ptr(), None, _lib.ptr(uc), _lib.ptr(qc), s)
+        ctx.bip = False
         ctx.rowterms = uc is not None
         ctx.rs = bool(rs)
-        ctx.save_for_backward(el, er, hc, hs if hs is not None else el.new_empty(0), lse, u,
+        ctx.save_for_backward(el, er, hc, el.new_empty(0), lse, u,
                               u_lo if u_lo is not None else el.new_empty(0),
                               ar if rs else el.new_empty(0),
                               *((uc, qc) if uc is not None else ()))
-        if v is None:
-            return u
-        return u, v
+        return u
 
     @staticmethod
     def backward(ctx, dU, dV=None):
-        if ctx.bip:
-            return _bip_bwd(ctx, dU, dV)
-        el, er, hc, hs, lse, u, u_lo, ar, *rowterms = ctx.saved_tensors
+        el, er, hc, hs, lse, *rest = ctx.saved_tensors
+        u, u_lo, ar, *rowterms = rest if rest else (None, el.new_empty(0), None)
         u_lo = u_lo if u_lo.numel() else None
         ar = ar if ctx.rs and not ctx.er_exact else None
-        graph = ctx.graph
         n, H = el.shape
-        m, _, F = hc.shape
-        dt = hc.dtype
-        dev = el.device
-        s = _stream(el)
-        g = graph.desc
-        dU = torch.zeros_like(u) if dU is None else _tc(dU, dt)
+        dt, dev = hc.dtype, el.device
+        dU = torch.zeros(n, H, hc.shape[2], device=dev, dtype=dt) if dU is None else _tc(dU, dt)
         use_dv = ctx.has_hs and dV is not None
         dV = _tc(dV, dt) if use_dv else None
-        E = max(graph.n_edges, 1)
-        d_el = torch.empty(n, H, device=dev, dtype=torch.float32)
-        if not use_dv and FUSED_BWD:
+        if not ctx.bip and not use_dv and FUSED_BWD:
+            d_el = torch.empty(n, H, device=dev, dtype=torch.float32)
             return _bwd_fused(ctx, el, er, hc, lse, u, u_lo, dU, d_el, hs, rowterms, ar)
-        # one (de, attd) record of 2H floats per edge: the column pass reads it as one
-        # 64-B segment at C4 (the CSC visits edges in random order)
-        rec = torch.empty(E, 2, H, device=dev, dtype=torch.float32)
-        de, attd = rec[:, 0], rec[:, 1]
-        d_hs = torch.empty(n, H, F, device=dev, dtype=dt) if use_dv else None
-        ev = _timed("edge_attention_bwd_rows")
-        _lib.call("msha_edge_attention_bwd_rows", g, H, F, _code(dt), el.data_ptr(),
-                  er.data_ptr(), hc.data_ptr(), lse.data_ptr(), u.data_ptr(), _lib.ptr(u_lo),
-                  dU.data_ptr(),
-                  hs.data_ptr() if use_dv else None, _lib.ptr(dV), None, ctx.slope, ctx.p,
-                  ctx.seed, 0, d_el.data_ptr(), de.data_ptr(), attd.data_ptr(), 2 * H,
-                  _lib.ptr(d_hs), s)
-        if ev is not None:
-            ev[1].record()
-        d_hc = torch.empty(m, H, F, device=dev, dtype=dt)
-        d_er = torch.empty(m, H, device=dev, dtype=torch.float32)
-        ev = _timed("csc_aggregate")
-        _csc_aggregate(graph, H, F, attd, de, dU, d_hc, d_er, s, ld=2 * H)
-        if ev is not None:
-            ev[1].record()
+        d_el, d_er, d_hc, d_hs = _inter_bwd(ctx.graph, ctx.bip, el, er, hc, lse, u, u_lo, dU, hs,
+                                            dV, None, ctx.slope, ctx.p, ctx.seed, timed=True)
         if ctx.has_hs and d_hs is None:
             d_hs = torch.zeros_like(hs)
         return d_el, d_er, d_hc, (d_hs if ctx.has_hs else None), None, None, None, None, None
@@ -330,34 +291,122 @@ def _bip_ws(graph, H, F, dev):
         _lib.fn("msha_bip_workspace_size")(graph.desc, H, F))))
 
 
-def _bip_bwd(ctx, dU, dV):
-    """Backward of the bipartite forward: one row pass (msha_bip_attention_bwd) gives
-    d_el, d_hs and the column gradients d_hc, d_er through per-wave LDS slabs."""
-    el, er, hc, hs, lse = ctx.saved_tensors
+# the bipartite kernels' block-partial reduce rides in the Ours layer's prep / finish
+# launches (msha_bip_defer_reduce; one graph node fewer each way); MSHA_BIP_DEFER=0: separate
+# reduce launches (A/B)
+BIP_DEFER_REDUCE = os.environ.get("MSHA_BIP_DEFER", "1") != "0"
+
+
+@contextlib.contextmanager
+def _deferred_reduce(on):
+    """While open (``on``), the block-partial reduce of a bipartite forward / backward is
+    handed to the next Ours-layer launch on the stream; leaving -- on an error too -- ends
+    the hand-over and launches a reduce that nothing took."""
+    if not on:
+        yield
+        return
+    _lib.call("msha_bip_defer_reduce", 1)
+    try:
+        yield
+    finally:
+        _lib.call("msha_bip_defer_reduce", 0)
+
+
+@contextlib.contextmanager
+def _events(name, on):
+    """KERNEL_EVENTS bracket of the launches inside (``on``: edge_attention's calls only)."""
+    ev = _timed(name) if on else None
+    yield
+    if ev is not None:
+        ev[1].record()
+
+
+# what the inter forward leaves: u (N,H,F), lse (N,H), v (M,H,F) with hs, the post-dropout
+# attention attd (E,H) where it was exported or the general kernels needed it, the bf16
+# rounding residual u_lo of u (general kernels only)
+_Inter = collections.namedtuple("_Inter", "bip u lse v attd u_lo")
+
+
+def _inter_fwd(graph, el, er, hc, hs, slope, p, seed, *, export_attd=False, keep_u_lo=False,
+               intra=None, timed=False):
+    """Inter attention forward, u and (with hs) v: one bipartite pass where bip_ok says so,
+    else msha_edge_attention_fwd + the CSC aggregate (needs hs).  ``intra(inter)``: the
+    caller's own launch on the result (the Ours layers' intra attention); on the bipartite
+    path it carries the v reduce (BIP_DEFER_REDUCE).  ``keep_u_lo``: a backward will follow."""
     n, H = el.shape
     m, _, F = hc.shape
-    dt = hc.dtype
-    dev = el.device
-    s = _stream(el)
-    g = ctx.graph.desc
-    dU = torch.zeros(n, H, F, device=dev, dtype=dt) if dU is None else _tc(dU, dt)
-    use_dv = ctx.has_hs and dV is not None
-    dV = _tc(dV, dt) if use_dv else None
+    dt, dev, s, g = hc.dtype, el.device, _stream(el), graph.desc
+    bip = bip_ok(graph, H, F, dt)
+    assert bip or hs is not None
+    u = torch.empty(n, H, F, device=dev, dtype=dt)
+    lse = torch.empty(n, H, device=dev, dtype=torch.float32)
+    v = torch.empty(m, H, F, device=dev, dtype=dt) if hs is not None else None
+    attd = u_lo = None
+    if export_attd or not bip:
+        attd = torch.empty(max(graph.n_edges, 1), H, device=dev, dtype=torch.float32)
+    with _deferred_reduce(bip and BIP_DEFER_REDUCE and intra is not None):
+        if bip:
+            ws = _bip_ws(graph, H, F, dev)
+            with _events("bip_attention_fwd", timed):
+                _lib.call("msha_bip_attention_fwd", g, H, F, _code(dt), el.data_ptr(),
+                          er.data_ptr(), hc.data_ptr(), _lib.ptr(hs), slope, p, seed, 0,
+                          u.data_ptr(), None, lse.data_ptr(), _lib.ptr(attd), _lib.ptr(v),
+                          ws.data_ptr(), ws.numel(), s)
+        else:
+            # bf16 tables under autograd: keep the rounding residual of u for the backward's
+            # D = dU . u (include/msha_gnn.h, u_lo)
+            u_lo = torch.empty_like(u) if dt == BF16 and keep_u_lo else None
+            with _events("edge_attention_fwd", timed):
+                _lib.call("msha_edge_attention_fwd", g, H, F, _code(dt), el.data_ptr(),
+                          er.data_ptr(), hc.data_ptr(), slope, p, seed, 0, u.data_ptr(),
+                          _lib.ptr(u_lo), lse.data_ptr(), attd.data_ptr(), s)
+            _csc_aggregate(graph, H, F, attd, None, hs, v, None, s)
+        inter = _Inter(bip, u, lse, v, attd, u_lo)
+        if intra is not None:
+            intra(inter)
+    return inter
+
+
+def _inter_bwd(graph, bip, el, er, hc, lse, u, u_lo, dU, hs, dV, row_coef, slope, p, seed, *,
+               intra=None, timed=False):
+    """Backward of _inter_fwd -> d_el, d_er, d_hc, d_hs (with hs and dV, else None): one
+    bipartite row pass (the column gradients through per-wave LDS slabs; u / u_lo unused),
+    else the row pass into one (de, attd) record of 2H floats per edge -- the column pass
+    reads it as one 64-B segment at C4, the CSC visits edges in random order -- and the CSC
+    aggregate.  ``intra(d_hs)``: the caller's launch after the row pass (the Ours layers'
+    stage 1); on the bipartite path it carries the d_hc / d_er reduce."""
+    n, H = el.shape
+    m, _, F = hc.shape
+    dt, dev, s, g = hc.dtype, el.device, _stream(el), graph.desc
     d_el = torch.empty(n, H, device=dev, dtype=torch.float32)
     d_er = torch.empty(m, H, device=dev, dtype=torch.float32)
     d_hc = torch.empty(m, H, F, device=dev, dtype=dt)
-    d_hs = torch.empty(n, H, F, device=dev, dtype=dt) if use_dv else None
-    ws = _bip_ws(ctx.graph, H, F, dev)
-    ev = _timed("bip_attention_bwd")
-    _lib.call("msha_bip_attention_bwd", g, H, F, _code(dt), el.data_ptr(), er.data_ptr(),
-              hc.data_ptr(), lse.data_ptr(), dU.data_ptr(), hs.data_ptr() if use_dv else None,
-              _lib.ptr(dV), None, ctx.slope, ctx.p, ctx.seed, 0, d_el.data_ptr(),
-              d_er.data_ptr(), d_hc.data_ptr(), _lib.ptr(d_hs), ws.data_ptr(), ws.numel(), s)
-    if ev is not None:
-        ev[1].record()
-    if ctx.has_hs and d_hs is None:
-        d_hs = torch.zeros_like(hs)
-    return d_el, d_er, d_hc, (d_hs if ctx.has_hs else None), None, None, None, None, None
+    d_hs = torch.empty(n, H, F, device=dev, dtype=dt) if dV is not None else None
+    hs = hs if dV is not None else None
+    if bip:
+        ws = _bip_ws(graph, H, F, dev)
+        with _deferred_reduce(BIP_DEFER_REDUCE and intra is not None):
+            with _events("bip_attention_bwd", timed):
+                _lib.call("msha_bip_attention_bwd", g, H, F, _code(dt), el.data_ptr(),
+                          er.data_ptr(), hc.data_ptr(), lse.data_ptr(), dU.data_ptr(),
+                          _lib.ptr(hs), _lib.ptr(dV), _lib.ptr(row_coef), slope, p, seed, 0,
+                          d_el.data_ptr(), d_er.data_ptr(), d_hc.data_ptr(), _lib.ptr(d_hs),
+                          ws.data_ptr(), ws.numel(), s)
+            if intra is not None:
+                intra(d_hs)
+        return d_el, d_er, d_hc, d_hs
+    rec = torch.empty(max(graph.n_edges, 1), 2, H, device=dev, dtype=torch.float32)
+    de, attd = rec[:, 0], rec[:, 1]
+    with _events("edge_attention_bwd_rows", timed):
+        _lib.call("msha_edge_attention_bwd_rows", g, H, F, _code(dt), el.data_ptr(),
+                  er.data_ptr(), hc.data_ptr(), lse.data_ptr(), u.data_ptr(), _lib.ptr(u_lo),
+                  dU.data_ptr(), _lib.ptr(hs), _lib.ptr(dV), _lib.ptr(row_coef), slope, p, seed,
+                  0, d_el.data_ptr(), de.data_ptr(), attd.data_ptr(), 2 * H, _lib.ptr(d_hs), s)
+    if intra is not None:
+        intra(d_hs)
+    with _events("csc_aggregate", timed):
+        _csc_aggregate(graph, H, F, attd, de, dU, d_hc, d_er, s, ld=2 * H)
+    return d_el, d_er, d_hc, d_hs
 
 
 # u-only backward as one column pass (msha_edge_attention_bwd_fused) instead of
@@ -2459,251 +2508,125 @@ def link_match_loss(h, rows, teacher_table, *, return_rows=False):
 
 
 # --------------------------------------------------------- full MSHA layer (Ours) ---
-# the bipartite kernels' block-partial reduce rides in the Ours layer's prep / finish
-# launches (msha_bip_defer_reduce; one graph node fewer each way); MSHA_BIP_DEFER=0: separate
-# reduce launches (A/B)
-BIP_DEFER_REDUCE = os.environ.get("MSHA_BIP_DEFER", "1") != "0"
-
-
 class _OursAttention(torch.autograd.Function):
-    """Ours.py:54-101 core: inter attention (u, v) + batch intra attention added to u."""
+    """Inter attention (u, v) exactly as edge_attention computes it, plus the batch intra
+    attention added to u, in one of two intra modes.
+    Joint (Ours.py:54-101; msha_ours_intra_fwd / _bwd): city and province under one
+    normaliser with the inter attention; its backward has a term into every inter row
+    (row_coef) and the score vectors a3s / a4s.
+    ``split`` (Ablation.py:165-202, OursLayer2; msha_ours_split_fwd / _bwd): city and
+    province each under its own softmax.  The intra weights are 1 / group size, so the
+    backward has no term into el / er / lse and a3s / a4s get exact zeros (their reference
+    gradient is rounding noise around 0); no attention export."""
 
     @staticmethod
     def forward(ctx, el, er, h1, h2, a3s, a4s, graph: Graph, groups, src, p: float, seed: int,
-                slope: float):
+                slope: float, split: bool):
         n, H = el.shape
         m, _, Fd = h1.shape
         dt = _table_dtype(h1, h2)
         el, er, h1, h2 = _f32c(el), _f32c(er), _tc(h1, dt), _tc(h2, dt)
-        a3s, a4s = _f32c(a3s), _f32c(a4s)
         src = src.to(torch.int64).contiguous()
         B = src.numel()
         dev = el.device
         s = _stream(el)
-        g = graph.desc
-        u_inter = torch.empty(n, H, Fd, device=dev, dtype=dt)
-        bip = bip_ok(graph, H, Fd, dt)
-        u_lo = (torch.empty_like(u_inter) if dt == BF16 and not bip
-                and any(ctx.needs_input_grad[:4]) else None)
-        lse = torch.empty(n, H, device=dev, dtype=torch.float32)
-        attd = torch.empty(max(graph.n_edges, 1), H, device=dev, dtype=torch.float32)
-        v = torch.empty(m, H, Fd, device=dev, dtype=dt)
+        if split:  # the score vectors are not read: only what their zero gradients look like
+            ctx.a_meta = (a3s.shape, a3s.dtype, a4s.shape, a4s.dtype)
+            scores = ()
+        else:
+            scores = (_f32c(a3s), _f32c(a4s))
         bstat = torch.empty(max(B, 1), H, 8, device=dev, dtype=torch.float32)
-        u = torch.empty_like(u_inter)
-        defer = bip and BIP_DEFER_REDUCE
-        try:
-            if bip:
-                # u, v and the attention export in one pass (msha_bip_attention_fwd); its v
-                # reduce runs inside the intra launch below (msha_bip_defer_reduce)
-                ws = _bip_ws(graph, H, Fd, dev)
-                if defer:
-                    _lib.call("msha_bip_defer_reduce", 1)
-                _lib.call("msha_bip_attention_fwd", g, H, Fd, _code(dt), el.data_ptr(),
-                          er.data_ptr(), h1.data_ptr(), h2.data_ptr(), slope, p, seed, 0,
-                          u_inter.data_ptr(), None, lse.data_ptr(), attd.data_ptr(),
-                          v.data_ptr(), ws.data_ptr(), ws.numel(), s)
+        u = torch.empty(n, H, Fd, device=dev, dtype=dt)
+        head = (graph.desc, groups.desc, B, src.data_ptr(), H, Fd, _code(dt), h2.data_ptr())
+
+        def intra(it):
+            if split:
+                _lib.call("msha_ours_split_fwd", *head, it.u.data_ptr(), p, seed, 0,
+                          bstat.data_ptr(), u.data_ptr(), s)
             else:
-                _lib.call("msha_edge_attention_fwd", g, H, Fd, _code(dt), el.data_ptr(),
-                          er.data_ptr(), h1.data_ptr(), slope, p, seed, 0, u_inter.data_ptr(),
-                          _lib.ptr(u_lo), lse.data_ptr(), attd.data_ptr(), s)
-                _csc_aggregate(graph, H, Fd, attd, None, h2, v, None, s)
-            _lib.call("msha_ours_intra_fwd", g, groups.desc, B, src.data_ptr(), H, Fd,
-                      _code(dt), h2.data_ptr(), a3s.data_ptr(), a4s.data_ptr(), el.data_ptr(),
-                      er.data_ptr(), lse.data_ptr(), u_inter.data_ptr(), slope, p, seed, 0,
-                      bstat.data_ptr(), u.data_ptr(), s)
-        finally:
-            if defer:
-                _lib.call("msha_bip_defer_reduce", 0)  # (launches it if still pending)
-        ctx.bip = bip
+                _lib.call("msha_ours_intra_fwd", *head, scores[0].data_ptr(),
+                          scores[1].data_ptr(), el.data_ptr(), er.data_ptr(), it.lse.data_ptr(),
+                          it.u.data_ptr(), slope, p, seed, 0, bstat.data_ptr(), u.data_ptr(), s)
+
+        # (bipartite: u, v and the joint mode's attention export in one pass)
+        it = _inter_fwd(graph, el, er, h1, h2, slope, p, seed, export_attd=not split,
+                        keep_u_lo=any(ctx.needs_input_grad[:4]), intra=intra)
+        ctx.bip, ctx.split = it.bip, split
         ctx.graph, ctx.groups, ctx.p, ctx.seed, ctx.slope = graph, groups, p, seed, slope
-        ctx.save_for_backward(el, er, h1, h2, a3s, a4s, lse, u_inter, bstat, src,
-                              u_lo if u_lo is not None else el.new_empty(0))
+        # the bipartite backward recomputes from (el, er, lse); the row form also reads the
+        # inter aggregate
+        empty = el.new_empty(0)
+        ctx.save_for_backward(el, er, h1, h2, it.lse, bstat, src, empty if it.bip else it.u,
+                              it.u_lo if it.u_lo is not None else empty, *scores)
         # post-dropout inter attention and batch statistics: outputs for record mode
-        ctx.mark_non_differentiable(attd, bstat)
+        attd = None if split else it.attd
+        ctx.mark_non_differentiable(*((bstat,) if split else (attd, bstat)))
         ctx.set_materialize_grads(False)  # no zero-filled gradients for attd / bstat
-        return u, v, attd, bstat
+        return u, it.v, attd, bstat
 
     @staticmethod
     def backward(ctx, dU, dV, _attd=None, _bstat=None):
-        el, er, h1, h2, a3s, a4s, lse, u_inter, bstat, src, u_lo = ctx.saved_tensors
+        el, er, h1, h2, lse, bstat, src, u_inter, u_lo, *scores = ctx.saved_tensors
         u_lo = u_lo if u_lo.numel() else None
-        graph, groups = ctx.graph, ctx.groups
+        graph, groups, split = ctx.graph, ctx.groups, ctx.split
         n, H = el.shape
         m, _, Fd = h1.shape
         B = src.numel()
         dev = el.device
         s = _stream(el)
-        g, gr = graph.desc, groups.desc
-        dt = h1.dtype
-        dU = torch.zeros_like(u_inter) if dU is None else _tc(dU, dt)
-        dV = torch.zeros(m, H, Fd, device=dev, dtype=dt) if dV is None else _tc(dV, dt)
-        G = torch.empty(max(B, 1), 2, H * Fd, device=dev, dtype=torch.float32)
-        bgrad = torch.empty(max(B, 1), H, 4, device=dev, dtype=torch.float32)
-        row_coef = torch.empty(n, H, device=dev, dtype=torch.float32)  # zeroed by stage 0
-        da3s = torch.empty(H, Fd, device=dev, dtype=torch.float32)
-        da4s = torch.empty(H, Fd, device=dev, dtype=torch.float32)
-        args = (g, gr, B, src.data_ptr(), H, Fd, _code(dt), h2.data_ptr(), a3s.data_ptr(),
-                a4s.data_ptr(),
-                bstat.data_ptr(), dU.data_ptr())
-        ws = _workspace(dev, _memo(groups, ("ours_ws", B, H, Fd), lambda: int(
-            _lib.fn("msha_ours_workspace_size")(gr, B, H, Fd))))
-        _lib.call("msha_ours_intra_bwd", *args, 0, ctx.slope, ctx.p, ctx.seed, 0, G.data_ptr(),
-                  bgrad.data_ptr(), row_coef.data_ptr(), da3s.data_ptr(), da4s.data_ptr(), None,
-                  ws.data_ptr(), ws.numel(), s)
-        E = max(graph.n_edges, 1)
-        d_el = torch.empty(n, H, device=dev, dtype=torch.float32)
-        d_hs = torch.empty(n, H, Fd, device=dev, dtype=dt)
-        d_hc = torch.empty(m, H, Fd, device=dev, dtype=dt)
-        d_er = torch.empty(m, H, device=dev, dtype=torch.float32)
-        if ctx.bip:
-            # row and column gradients of the inter attention in one pass; its d_hc / d_er
-            # reduce runs inside the intra stage-1 launch (msha_bip_defer_reduce)
-            ws = _bip_ws(graph, H, Fd, dev)
-            defer = BIP_DEFER_REDUCE
-            try:
-                if defer:
-                    _lib.call("msha_bip_defer_reduce", 1)
-                _lib.call("msha_bip_attention_bwd", g, H, Fd, _code(dt), el.data_ptr(),
-                          er.data_ptr(), h1.data_ptr(), lse.data_ptr(), dU.data_ptr(),
-                          h2.data_ptr(), dV.data_ptr(), row_coef.data_ptr(), ctx.slope, ctx.p,
-                          ctx.seed, 0, d_el.data_ptr(), d_er.data_ptr(), d_hc.data_ptr(),
-                          d_hs.data_ptr(), ws.data_ptr(), ws.numel(), s)
-                _lib.call("msha_ours_intra_bwd", *args, 1, ctx.slope, ctx.p, ctx.seed, 0,
-                          G.data_ptr(), bgrad.data_ptr(), None, None, None, d_hs.data_ptr(),
-                          None, 0, s)
-            finally:
-                if defer:
-                    _lib.call("msha_bip_defer_reduce", 0)
-            return d_el, d_er, d_hc, d_hs, da3s, da4s, None, None, None, None, None, None
-        rec = torch.empty(E, 2, H, device=dev, dtype=torch.float32)  # (de, attd) per edge
-        de, attd = rec[:, 0], rec[:, 1]
-        _lib.call("msha_edge_attention_bwd_rows", g, H, Fd, _code(dt), el.data_ptr(), er.data_ptr(),
-                  h1.data_ptr(), lse.data_ptr(), u_inter.data_ptr(), _lib.ptr(u_lo), dU.data_ptr(),
-                  h2.data_ptr(), dV.data_ptr(), row_coef.data_ptr(), ctx.slope, ctx.p, ctx.seed,
-                  0, d_el.data_ptr(), de.data_ptr(), attd.data_ptr(), 2 * H, d_hs.data_ptr(), s)
-        _lib.call("msha_ours_intra_bwd", *args, 1, ctx.slope, ctx.p, ctx.seed, 0, G.data_ptr(),
-                  bgrad.data_ptr(), None, None, None, d_hs.data_ptr(), None, 0, s)
-        _csc_aggregate(graph, H, Fd, attd, de, dU, d_hc, d_er, s, ld=2 * H)
-        return d_el, d_er, d_hc, d_hs, da3s, da4s, None, None, None, None, None, None
-
-
-class _OursSplitAttention(torch.autograd.Function):
-    """Ablation.py:165-202 core (OursLayer2): the inter attention (u, v) exactly as
-    edge_attention computes it, plus the batch intra attention with city and province each
-    under its own softmax, added to u (msha_ours_split_fwd / _bwd).  The intra weights are
-    1 / group size, so the backward has no term into el / er / lse and a3s / a4s get exact
-    zeros (their reference gradient is rounding noise around 0)."""
-
-    @staticmethod
-    def forward(ctx, el, er, h1, h2, a3s, a4s, graph: Graph, groups, src, p: float, seed: int,
-                slope: float):
-        n, H = el.shape
-        m, _, Fd = h1.shape
-        dt = _table_dtype(h1, h2)
-        el, er, h1, h2 = _f32c(el), _f32c(er), _tc(h1, dt), _tc(h2, dt)
-        src = src.to(torch.int64).contiguous()
-        B = src.numel()
-        dev = el.device
-        s = _stream(el)
-        g = graph.desc
-        u_inter = torch.empty(n, H, Fd, device=dev, dtype=dt)
-        bip = bip_ok(graph, H, Fd, dt)
-        u_lo = (torch.empty_like(u_inter) if dt == BF16 and not bip
-                and any(ctx.needs_input_grad[:4]) else None)
-        lse = torch.empty(n, H, device=dev, dtype=torch.float32)
-        v = torch.empty(m, H, Fd, device=dev, dtype=dt)
-        bstat = torch.empty(max(B, 1), H, 8, device=dev, dtype=torch.float32)
-        u = torch.empty_like(u_inter)
-        defer = bip and BIP_DEFER_REDUCE
-        try:
-            if bip:
-                ws = _bip_ws(graph, H, Fd, dev)
-                if defer:
-                    _lib.call("msha_bip_defer_reduce", 1)
-                _lib.call("msha_bip_attention_fwd", g, H, Fd, _code(dt), el.data_ptr(),
-                          er.data_ptr(), h1.data_ptr(), h2.data_ptr(), slope, p, seed, 0,
-                          u_inter.data_ptr(), None, lse.data_ptr(), None, v.data_ptr(),
-                          ws.data_ptr(), ws.numel(), s)
-            else:
-                attd = torch.empty(max(graph.n_edges, 1), H, device=dev, dtype=torch.float32)
-                _lib.call("msha_edge_attention_fwd", g, H, Fd, _code(dt), el.data_ptr(),
-                          er.data_ptr(), h1.data_ptr(), slope, p, seed, 0, u_inter.data_ptr(),
-                          _lib.ptr(u_lo), lse.data_ptr(), attd.data_ptr(), s)
-                _csc_aggregate(graph, H, Fd, attd, None, h2, v, None, s)
-            _lib.call("msha_ours_split_fwd", g, groups.desc, B, src.data_ptr(), H, Fd,
-                      _code(dt), h2.data_ptr(), u_inter.data_ptr(), p, seed, 0,
-                      bstat.data_ptr(), u.data_ptr(), s)
-        finally:
-            if defer:
-                _lib.call("msha_bip_defer_reduce", 0)  # (launches it if still pending)
-        ctx.bip = bip
-        ctx.graph, ctx.groups, ctx.p, ctx.seed, ctx.slope = graph, groups, p, seed, slope
-        ctx.a_meta = (a3s.shape, a3s.dtype, a4s.shape, a4s.dtype)
-        # the bipartite backward recomputes from (el, er, lse); the row form also reads the
-        # inter aggregate.  The score vectors are not saved: nothing depends on them.
-        empty = el.new_empty(0)
-        ctx.save_for_backward(el, er, h1, h2, lse, bstat, src, empty if bip else u_inter,
-                              u_lo if u_lo is not None else empty)
-        ctx.mark_non_differentiable(bstat)
-        ctx.set_materialize_grads(False)
-        return u, v, bstat
-
-    @staticmethod
-    def backward(ctx, dU, dV, _bstat=None):
-        el, er, h1, h2, lse, bstat, src, u_inter, u_lo = ctx.saved_tensors
-        u_lo = u_lo if u_lo.numel() else None
-        graph, groups = ctx.graph, ctx.groups
-        n, H = el.shape
-        m, _, Fd = h1.shape
-        B = src.numel()
-        dev = el.device
-        s = _stream(el)
-        g, gr = graph.desc, groups.desc
         dt = h1.dtype
         dU = torch.zeros(n, H, Fd, device=dev, dtype=dt) if dU is None else _tc(dU, dt)
         dV = torch.zeros(m, H, Fd, device=dev, dtype=dt) if dV is None else _tc(dV, dt)
         G = torch.empty(max(B, 1), 2, H * Fd, device=dev, dtype=torch.float32)
-        das = torch.empty(2, H, Fd, device=dev, dtype=torch.float32)  # zeroed by stage 0
-        args = (g, gr, B, src.data_ptr(), H, Fd, _code(dt), bstat.data_ptr())
-        ws = _workspace(dev, _memo(groups, ("ours_ws", B, H, Fd), lambda: int(
-            _lib.fn("msha_ours_split_workspace_size")(gr, B, H, Fd))))
-        _lib.call("msha_ours_split_bwd", *args, dU.data_ptr(), 0, ctx.p, ctx.seed, 0,
-                  G.data_ptr(), das[0].data_ptr(), das[1].data_ptr(), None, ws.data_ptr(),
-                  ws.numel(), s)
-        d_el = torch.empty(n, H, device=dev, dtype=torch.float32)
-        d_hs = torch.empty(n, H, Fd, device=dev, dtype=dt)
-        d_hc = torch.empty(m, H, Fd, device=dev, dtype=dt)
-        d_er = torch.empty(m, H, device=dev, dtype=torch.float32)
-        sh3, dt3, sh4, dt4 = ctx.a_meta
-        da3s, da4s = das[0].view(sh3).to(dt3), das[1].view(sh4).to(dt4)
-        if ctx.bip:
-            ws = _bip_ws(graph, H, Fd, dev)
-            defer = BIP_DEFER_REDUCE
-            try:
-                if defer:
-                    _lib.call("msha_bip_defer_reduce", 1)
-                _lib.call("msha_bip_attention_bwd", g, H, Fd, _code(dt), el.data_ptr(),
-                          er.data_ptr(), h1.data_ptr(), lse.data_ptr(), dU.data_ptr(),
-                          h2.data_ptr(), dV.data_ptr(), None, ctx.slope, ctx.p, ctx.seed, 0,
-                          d_el.data_ptr(), d_er.data_ptr(), d_hc.data_ptr(), d_hs.data_ptr(),
-                          ws.data_ptr(), ws.numel(), s)
-                _lib.call("msha_ours_split_bwd", *args, None, 1, ctx.p, ctx.seed, 0,
-                          G.data_ptr(), None, None, d_hs.data_ptr(), None, 0, s)
-            finally:
-                if defer:
-                    _lib.call("msha_bip_defer_reduce", 0)
-            return d_el, d_er, d_hc, d_hs, da3s, da4s, None, None, None, None, None, None
-        E = max(graph.n_edges, 1)
-        rec = torch.empty(E, 2, H, device=dev, dtype=torch.float32)  # (de, attd) per edge
-        de, attd = rec[:, 0], rec[:, 1]
-        _lib.call("msha_edge_attention_bwd_rows", g, H, Fd, _code(dt), el.data_ptr(), er.data_ptr(),
-                  h1.data_ptr(), lse.data_ptr(), u_inter.data_ptr(), _lib.ptr(u_lo), dU.data_ptr(),
-                  h2.data_ptr(), dV.data_ptr(), None, ctx.slope, ctx.p, ctx.seed, 0,
-                  d_el.data_ptr(), de.data_ptr(), attd.data_ptr(), 2 * H, d_hs.data_ptr(), s)
-        _lib.call("msha_ours_split_bwd", *args, None, 1, ctx.p, ctx.seed, 0, G.data_ptr(), None,
-                  None, d_hs.data_ptr(), None, 0, s)
-        _csc_aggregate(graph, H, Fd, attd, de, dU, d_hc, d_er, s, ld=2 * H)
-        return d_el, d_er, d_hc, d_hs, da3s, da4s, None, None, None, None, None, None
+        size_fn = "msha_ours_split_workspace_size" if split else "msha_ours_workspace_size"
+        ws = _workspace(dev, _memo(groups, (size_fn, B, H, Fd), lambda: int(
+            _lib.fn(size_fn)(groups.desc, B, H, Fd))))
+        head = (graph.desc, groups.desc, B, src.data_ptr(), H, Fd, _code(dt))
+        # stage 0 (zeroes what it accumulates into), the inter row pass, stage 1
+        if split:
+            row_coef = None
+            das = torch.empty(2, H, Fd, device=dev, dtype=torch.float32)
+            head += (bstat.data_ptr(),)
+            tail = (ctx.p, ctx.seed, 0, G.data_ptr())
+            _lib.call("msha_ours_split_bwd", *head, dU.data_ptr(), 0, *tail, das[0].data_ptr(),
+                      das[1].data_ptr(), None, ws.data_ptr(), ws.numel(), s)
+            sh3, dt3, sh4, dt4 = ctx.a_meta  # (das is final: the zeros stage 0 wrote)
+            da3s, da4s = das[0].view(sh3).to(dt3), das[1].view(sh4).to(dt4)
+
+            def intra(d_hs):
+                _lib.call("msha_ours_split_bwd", *head, None, 1, *tail, None, None,
+                          d_hs.data_ptr(), None, 0, s)
+        else:
+            bgrad = torch.empty(max(B, 1), H, 4, device=dev, dtype=torch.float32)
+            row_coef = torch.empty(n, H, device=dev, dtype=torch.float32)
+            da3s = torch.empty(H, Fd, device=dev, dtype=torch.float32)
+            da4s = torch.empty(H, Fd, device=dev, dtype=torch.float32)
+            head += (h2.data_ptr(), scores[0].data_ptr(), scores[1].data_ptr(), bstat.data_ptr(),
+                     dU.data_ptr())
+            tail = (ctx.slope, ctx.p, ctx.seed, 0, G.data_ptr(), bgrad.data_ptr())
+            _lib.call("msha_ours_intra_bwd", *head, 0, *tail, row_coef.data_ptr(),
+                      da3s.data_ptr(), da4s.data_ptr(), None, ws.data_ptr(), ws.numel(), s)
+
+            def intra(d_hs):
+                _lib.call("msha_ours_intra_bwd", *head, 1, *tail, None, None, None,
+                          d_hs.data_ptr(), None, 0, s)
+        d_el, d_er, d_hc, d_hs = _inter_bwd(graph, ctx.bip, el, er, h1, lse, u_inter, u_lo, dU, h2,
+                                            dV, row_coef, ctx.slope, ctx.p, ctx.seed, intra=intra)
+        return d_el, d_er, d_hc, d_hs, da3s, da4s, None, None, None, None, None, None, None
+
+
+def _ours_apply(name, split, graph, groups, src, el, er, h1, h2, a3s, a4s, p, training, slope,
+                seed):
+    _lib.require_cuda(el, er, h1, h2, a3s, a4s, src)
+    H, Fd = el.shape[1], h1.shape[-1]
+    if not _lib.load().msha_edge_attention_supported(H, Fd):
+        raise NotImplementedError(f"{name}: (heads={H}, feat={Fd}) not compiled")
+    if H * Fd > 512:
+        raise NotImplementedError(f"{name}: heads*feat must be <= 512")
+    p = float(p) if training else 0.0
+    if seed is None:
+        seed = new_seed() if p > 0 else 0
+    return _OursAttention.apply(el, er, h1, h2, a3s, a4s, graph, groups, src, p, seed, slope, split)
 
 
 def ours_attention(graph: Graph, groups, src, el, er, h1, h2, a3s, a4s, p: float = 0.0,
@@ -2711,17 +2634,8 @@ def ours_attention(graph: Graph, groups, src, el, er, h1, h2, a3s, a4s, p: float
                    return_aux: bool = False):
     """Full MSHA attention core (Ours.py:54-101): returns (u, v), u = inter + intra;
     with return_aux also (attd (E, H) post-dropout inter attention, bstat (B, H, 8))."""
-    _lib.require_cuda(el, er, h1, h2, a3s, a4s, src)
-    H, Fd = el.shape[1], h1.shape[-1]
-    if not _lib.load().msha_edge_attention_supported(H, Fd):
-        raise NotImplementedError(f"ours_attention: (heads={H}, feat={Fd}) not compiled")
-    if H * Fd > 512:
-        raise NotImplementedError("ours_attention: heads*feat must be <= 512")
-    p = float(p) if training else 0.0
-    if seed is None:
-        seed = new_seed() if p > 0 else 0
-    u, v, attd, bstat = _OursAttention.apply(el, er, h1, h2, a3s, a4s, graph, groups, src, p,
-                                             seed, slope)
+    u, v, attd, bstat = _ours_apply("ours_attention", False, graph, groups, src, el, er, h1, h2,
+                                    a3s, a4s, p, training, slope, seed)
     return (u, v, attd, bstat) if return_aux else (u, v)
 
 
@@ -2733,17 +2647,8 @@ def ours_split_attention(graph: Graph, groups, src, el, er, h1, h2, a3s, a4s, p:
     (u, v); with return_aux also bstat (B, H, 8) (the intra weights 1 / group size in slots
     5 / 6).  a3s / a4s cannot change the output and get exact zero gradients; the dropout
     draws are ``ours_attention``'s (same Philox keys)."""
-    _lib.require_cuda(el, er, h1, h2, a3s, a4s, src)
-    H, Fd = el.shape[1], h1.shape[-1]
-    if not _lib.load().msha_edge_attention_supported(H, Fd):
-        raise NotImplementedError(f"ours_split_attention: (heads={H}, feat={Fd}) not compiled")
-    if H * Fd > 512:
-        raise NotImplementedError("ours_split_attention: heads*feat must be <= 512")
-    p = float(p) if training else 0.0
-    if seed is None:
-        seed = new_seed() if p > 0 else 0
-    u, v, bstat = _OursSplitAttention.apply(el, er, h1, h2, a3s, a4s, graph, groups, src, p,
-                                            seed, slope)
+    u, v, _, bstat = _ours_apply("ours_split_attention", True, graph, groups, src, el, er, h1, h2,
+                                 a3s, a4s, p, training, slope, seed)
     return (u, v, bstat) if return_aux else (u, v)
 
 

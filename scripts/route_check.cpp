@@ -1,5 +1,6 @@
-// Stand-alone host check of the resident-W route predicates (csrc/skinny_route.h) for a
-// sanitizer build: plain C++, no device, no library.
+// Stand-alone host check of the route predicates -- the resident-W kernels'
+// (csrc/skinny_route.h) and the bipartite attention's (csrc/bip_route.h) -- for a sanitizer
+// build: plain C++, no device, no library.
 //
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
 //       -Xarch_host -fno-sanitize-recover=undefined scripts/route_check.cpp -o route_check
@@ -11,9 +12,11 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "../msha--gnn_amd/csrc/bip_route.h"
 #include "../msha--gnn_amd/csrc/skinny_route.h"
 
 using namespace msha::route;
+namespace br = msha::bip_route;
 
 static int g_bad = 0, g_n = 0;
 static void expect(int got, int want, const char* what, long long a = 0, long long b = 0,
@@ -25,7 +28,81 @@ static void expect(int got, int want, const char* what, long long a = 0, long lo
   }
 }
 
+// The bipartite attention's route (csrc/bip_route.h) against the rule as DESIGN §4 states
+// it, written out here a second time in the order of the table: every knob combination,
+// cut - 1 and cut, u_lo, a null rowmask, slopes outside [0, 1], the 2^31 byte limits and
+// the shapes the mask kernels do not serve.  Returns how many calls reached each kind.
+static void check_bip(int (&seen)[2][4]) {
+  struct Shape {
+    int heads, feat;
+    int64_t m;
+    bool covered;  // by the walk's shape rule
+  };
+  const Shape shapes[] = {{2, 64, 32, true},  {2, 64, 20, true},  {2, 64, 33, false}, {8, 16, 8, true},
+                          {8, 16, 9, false},  {1, 64, 17, true},  {2, 128, 16, true}, {2, 128, 17, false},
+                          {4, 32, 16, true},  {4, 64, 16, true},  {4, 64, 17, false}, {2, 16, 8, false},
+                          {16, 8, 4, false},  {1, 192, 8, false}, {0, 64, 8, false},  {2, 0, 8, false}};
+  const int64_t cut = 256;
+  for (const Shape& sh : shapes)
+    for (int esize : {4, 2, 0})
+      for (int64_t bip2 : {1, 0})
+        for (int64_t bip3 : {1, 0})
+          for (int bwd32 : {-1, 0, 1})
+            for (int64_t rows : {cut - 1, cut})
+              for (int flags = 0; flags < 8; ++flags)
+                for (float slope : {0.2f, 0.f, 1.f, -0.1f, 1.5f}) {
+                  const bool u_lo = flags & 1, rowmask = !(flags & 2), drop = flags & 4;
+                  const bool compiled = sh.heads >= 1 && sh.heads <= 8 && sh.feat >= 8 && sh.feat <= 128;
+                  const br::Call c{rows, sh.m, rows * 2, rowmask, sh.heads, sh.feat, esize, compiled,
+                                   slope, drop, u_lo};
+                  const br::Route r = br::route(c, br::Knobs{bip2, bip3, bwd32, cut});
+                  int fwd = br::kNone, bwd = br::kNone;
+                  if (sh.covered && esize != 0) {
+                    const bool maskable = bip2 != 0 && sh.heads == 2 && sh.feat == 64 && rowmask &&
+                                          slope >= 0.f && slope <= 1.f;
+                    if (u_lo || !maskable) fwd = br::kWalk;
+                    else if (rows >= cut && bip3 != 0) fwd = br::kMfma;
+                    else fwd = br::kMask;
+                    if (!maskable || rows < cut) bwd = br::kWalk;
+                    else if (bip3 != 0 && (esize == 2 || bwd32 == 1 || (bwd32 < 0 && !drop))) bwd = br::kMfma;
+                    else bwd = br::kMask;
+                  }
+                  expect(r.fwd, fwd, "bip fwd", sh.heads, sh.feat, flags);
+                  expect(r.bwd, bwd, "bip bwd", sh.heads, sh.feat, flags);
+                  ++seen[0][r.fwd];
+                  ++seen[1][r.bwd];
+                }
+  // the byte limits: n_rows H F 4 and n_edges H 4 (covered); n_edges 8 (maskable; at 2 x 64
+  // the same bound as the covered one, so it never decides alone)
+  const br::Knobs k{1, 1, -1, 131072};
+  auto at = [&](int64_t rows, int64_t edges, int heads, int feat, int64_t m) {
+    return br::route(br::Call{rows, m, edges, true, heads, feat, 4, true, 0.2f, false, false}, k);
+  };
+  const int64_t r128 = br::k2G / (128 * 4), r256 = br::k2G / (256 * 4);
+  expect(at(r128 - 1, 8, 2, 64, 32).fwd, br::kMfma, "bip rows below 2^31 bytes", r128 - 1);
+  expect(at(r128 - 1, 8, 2, 64, 32).bwd, br::kMfma, "bip rows below 2^31 bytes, bwd", r128 - 1);
+  expect(at(r128, 8, 2, 64, 32).fwd, br::kNone, "bip rows at 2^31 bytes", r128);
+  expect(at(r256 - 1, 8, 4, 64, 16).fwd, br::kWalk, "bip 4 x 64 rows below 2^31 bytes", r256 - 1);
+  expect(at(r256, 8, 4, 64, 16).bwd, br::kNone, "bip 4 x 64 rows at 2^31 bytes", r256);
+  expect(at(1000, br::k2G / 8 - 1, 2, 64, 32).fwd, br::kMask, "bip edges below 2^31 bytes");
+  expect(at(1000, br::k2G / 8, 2, 64, 32).fwd, br::kNone, "bip edges at 2^31 bytes");
+  expect(at(1000, br::k2G / 32, 8, 16, 8).fwd, br::kNone, "bip 8 heads edges at 2^31 bytes");
+  expect(at(1000, br::k2G / 32 - 1, 8, 16, 8).fwd, br::kWalk, "bip 8 heads edges below 2^31 bytes");
+  expect(at(INT64_MAX / 2, 8, 2, 64, 32).fwd, br::kNone, "bip huge rows");
+  expect(at(1000, INT64_MAX / 2, 2, 64, 32).bwd, br::kNone, "bip huge edges");
+  expect(at(0, 0, 2, 64, 32).fwd, br::kNone, "bip no rows");
+  expect(at(1000, 8, 2, 64, 0).fwd, br::kNone, "bip no columns");
+  // (heads, feat) outside the compiled set, whatever else holds
+  expect(br::route(br::Call{1000, 32, 2000, true, 2, 64, 4, false, 0.2f, false, false}, k).fwd, br::kNone,
+         "bip not compiled");
+  // MSHA_BIP3_BWD32 above 1 forces the MFMA backward like 1 does
+  expect(br::route(br::Call{1000, 32, 2000, true, 2, 64, 4, true, 0.2f, true, false}, br::Knobs{1, 1, 2, 0}).bwd,
+         br::kMfma, "bip bwd32 = 2");
+}
+
 int main() {
+  int bip_seen[2][4] = {};
+  check_bip(bip_seen);
   const uintptr_t base = (uintptr_t)1 << 30;
   const int64_t split_min = 65536;
   const int64_t ks[2] = {128, 64};
@@ -129,6 +206,11 @@ int main() {
       expect(dx(true, 2048, N, K, base, base, base, (int)(K / 16), 16, false), kTiled, "dx no term", K, N);
       expect(dx(true, 2048, N, K, base, base, base + 4, (int)(K / 16), 16, true), kTiled, "dx C + 4", K, N);
     }
+  for (int d = 0; d < 2; ++d) {
+    std::printf("bip %s: %d none, %d walk, %d mask, %d mfma\n", d ? "bwd" : "fwd", bip_seen[d][0],
+                bip_seen[d][1], bip_seen[d][2], bip_seen[d][3]);
+    for (int kind = 0; kind < 4; ++kind) expect(bip_seen[d][kind] > 0, 1, "bip kind reached", d, kind);
+  }
   std::printf("route_check: %d checks, %d mismatches, %d covered projection calls\n", g_n, g_bad, reached);
   return g_bad != 0;
 }

@@ -1,8 +1,11 @@
-"""Bipartite small-M kernels (msha_bip_attention_fwd/_bwd, csrc/edge_bip.hip): the
-repo's adjacency shape, N sources x M <= 32 recipients (every shipped year; bip1m).
-u, v, lse, the attention export and every gradient against the fp64 oracle on the
-stored values (fp32 1e-5, bf16 1e-2) and against the general kernels they replace
-(functional.BIP = False), with virtual rows, a hot column, full rows, dropout (the
+"""Bipartite small-M kernels (msha_bip_attention_fwd/_bwd): the repo's adjacency shape,
+N sources x M <= 32 recipients (every shipped year; bip1m), in its three kernel families --
+the CSR walk (csrc/edge_bip.hip, every covered shape) and, for 2 heads x 64 on graphs with
+row masks, the mask kernels (edge_bip2.hip) and the MFMA kernels (edge_bip3.hip).  Which
+family a case runs is asserted from msha_bip_route (the ``bip_path`` settings) before its
+numbers are compared.  u, v, lse, the attention export and every gradient against the fp64
+oracle on the stored values (fp32 1e-5, bf16 1e-2) and against the general kernels they
+replace (functional.BIP = False), with virtual rows, a hot column, full rows, dropout (the
 kernels' Philox masks injected) and groups that straddle keep-bit pages."""
 import numpy as np
 import pytest
@@ -15,19 +18,56 @@ from test_gpu_kernels import _keep_mask
 pytestmark = pytest.mark.gpu
 
 
+WALK, MASK, MFMA = 1, 2, 3
+
+
+class BipPath(str):
+    """A bipartite setting's name, with the kernel families it must reach: a test that takes
+    the setting calls ``expect`` for its graph and call, which asserts msha_bip_route --
+    the function the launches themselves ask -- against the table below before any number
+    is compared (a setting that silently ran another kernel would prove nothing)."""
+
+    checked = 0
+
+    def expect(self, graph, H, F, dtype, p=0.0):
+        from msha_gnn_amd import _lib
+
+        bf = dtype == torch.bfloat16
+        if (H, F) != (2, 64):
+            want = (WALK, WALK)  # the mask and MFMA kernels are 2 x 64 only
+        elif self == "default":
+            assert graph.n_rows < 131072
+            want = (MASK, WALK)
+        elif self == "mfma":  # MSHA_BIP3_BWD32=0: the fp32 backward stays on the mask kernel
+            want = (MFMA, MFMA if bf else MASK)
+        else:
+            want = (MFMA, MFMA)
+        code = int(_lib.fn("msha_bip_route")(graph.desc, H, F, 1 if bf else 0, 0.2, p, 0))
+        assert (code % 16, code // 16) == want, (str(self), H, F, dtype, p)
+        self.checked += 1
+
+
+def _bip_setting(name, monkeypatch):
+    from msha_gnn_amd import _lib
+
+    monkeypatch.setenv("MSHA_BIP3_BWD32", "1" if name == "mfma_bwd32" else "0")
+    prev = _lib.fn("msha_bip2_bwd_min_rows")(-1 if name == "default" else 0)
+    path = BipPath(name)
+    yield path
+    _lib.fn("msha_bip2_bwd_min_rows")(prev)
+    assert path.checked, "the test did not assert its route (BipPath.expect)"
+
+
 @pytest.fixture(params=["default", "mfma", "mfma_bwd32"])
 def bip_path(request, msha, monkeypatch):
     """The library's size-based choice ("default": below 131,072 rows the mask forward and
     the CSR-walk backward) and the large-graph choice forced on every 2 x 64, M <= 32 graph
     ("mfma": msha_bip2_bwd_min_rows(0) with MSHA_BIP3_BWD32=0: the MFMA kernels of
     edge_bip3.hip, but the fp32 backward on edge_bip2.hip's mask kernel; "mfma_bwd32": the
-    MFMA backward for fp32 too, the library's large-graph default since round 6)."""
-    from msha_gnn_amd import _lib
+    MFMA backward for fp32 too, the library's large-graph default without dropout).  Other
+    shapes run the CSR walk of edge_bip.hip in every setting."""
+    yield from _bip_setting(request.param, monkeypatch)
 
-    monkeypatch.setenv("MSHA_BIP3_BWD32", "1" if request.param == "mfma_bwd32" else "0")
-    prev = _lib.fn("msha_bip2_bwd_min_rows")(-1 if request.param == "default" else 0)
-    yield request.param
-    _lib.fn("msha_bip2_bwd_min_rows")(prev)
 
 CASES = [
     # (n, m, H, F, max_deg, extra); M * H <= 64 (one row's slots fit one group)
@@ -78,6 +118,7 @@ def test_bip_vs_oracle_and_general(cuda, msha, bip_path, case, p, dtype):
     graph = Graph.from_dense(t(c, cuda))
     code = 1 if dtype == torch.bfloat16 else 0
     assert _lib.load().msha_bip_supported(graph.desc, H, F, code) == 1
+    bip_path.expect(graph, H, F, dtype, p)
     seed = 31
     tol = 1e-5 if dtype == torch.float32 else 1e-2
     got = _run(MF, graph, el, er, hc, hs, dU, dV, p, seed, cuda, dtype, True)
@@ -116,6 +157,7 @@ def test_bip_raw_abi_lse_attd_deterministic(cuda, msha, bip_path):
     hs = rng.standard_normal((n, H, F)).astype(np.float32)
     graph = Graph.from_dense(t(c, cuda))
     g = graph.desc
+    bip_path.expect(graph, H, F, torch.float32)
     L = _lib.load()
     E = graph.n_edges
     ws = torch.empty(int(L.msha_bip_workspace_size(g, H, F)), dtype=torch.uint8, device=cuda)
@@ -181,6 +223,7 @@ def test_bip_many_groups_per_wave_vs_general(cuda, msha, bip_path, p):
     hs = rng.standard_normal((n, H, F)).astype(np.float32)
     dU = rng.standard_normal((n, H, F)).astype(np.float32)
     dV = rng.standard_normal((m, H, F)).astype(np.float32)
+    bip_path.expect(graph, H, F, torch.float32, p)
     got = _run(MF, graph, el, er, hc, hs, dU, dV, p, 13, cuda, torch.float32, True)
     gen = _run(MF, graph, el, er, hc, hs, dU, dV, p, 13, cuda, torch.float32, False)
     keep = _keep_mask(graph.n_edges, H, p, 13, cuda)
@@ -231,12 +274,7 @@ def test_shipped_graph_models_run_on_the_bipartite_kernels(cuda, msha):
 def mask_bwd_everywhere(msha, monkeypatch):
     """Route every M <= 32, 2 x 64 graph through the MFMA kernels (edge_bip3.hip, the fp32
     backward included), not only those above the 131,072-row cut (msha_bip2_bwd_min_rows)."""
-    from msha_gnn_amd import _lib
-
-    monkeypatch.setenv("MSHA_BIP3_BWD32", "1")
-    prev = _lib.fn("msha_bip2_bwd_min_rows")(0)
-    yield
-    _lib.fn("msha_bip2_bwd_min_rows")(prev)
+    yield from _bip_setting("mfma_bwd32", monkeypatch)
 
 
 @pytest.mark.parametrize("p", [0.0, 0.4])
@@ -245,4 +283,5 @@ def test_ours_attention_mask_backward(cuda, msha, mask_bwd_everywhere, p):
     variants of bip3_bwd_kernel against the dense fp64 restatement."""
     from test_gpu_ours import check_ours_attention_vs_dense
 
-    check_ours_attention_vs_dense(cuda, p)
+    check_ours_attention_vs_dense(cuda, p, on_graph=lambda g, H, F, dt: mask_bwd_everywhere.expect(
+        g, H, F, dt, p))

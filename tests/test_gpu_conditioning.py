@@ -225,6 +225,7 @@ def test_bip_vs_oracle(cuda, msha, bip_path, key, dtype, regime, p):  # noqa: F8
     x, graph = _case(key, cuda)
     _, _, H, F = x["shape"]
     assert _lib.load().msha_bip_supported(graph.desc, H, F, 1 if dtype == BF16 else 0) == 1
+    bip_path.expect(graph, H, F, dtype, p)
     _check_uv(f"bip-{bip_path}", _bip_runner, key, regime, p, dtype, cuda)
 
 
@@ -334,4 +335,6 @@ def test_scale_invariance_fused(cuda, msha, rowterms, dtype, p):
 @pytest.mark.parametrize("p", [0.0, 0.5])
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
 def test_scale_invariance_bip(cuda, msha, bip_path, dtype, p):  # noqa: F811
+    x, graph = _case("B1", cuda)
+    bip_path.expect(graph, x["shape"][2], x["shape"][3], dtype, p)
     _uv_scaling(_bip_runner, "B1", p, dtype, cuda)

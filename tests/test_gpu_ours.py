@@ -87,7 +87,7 @@ def _dense_ours_core(el, er, h1, h2, a3s, a4s, mask, city, prov, src, keep_e=Non
 
 
 def check_ours_attention_vs_dense(cuda, p, dtype=torch.float32, tol_out=1e-5, tol_grad=1e-4,
-                                  score_hook=None):
+                                  score_hook=None, on_graph=None):
     """ours_attention (u, v and every input gradient) against the dense fp64 restatement
     with the kernels' dropout masks; ``dtype`` = storage of the node tables h1 / h2 (bf16:
     the reference is fed the same bf16-rounded tables and upstream gradients).
@@ -135,6 +135,8 @@ def check_ours_attention_vs_dense(cuda, p, dtype=torch.float32, tol_out=1e-5, to
         h1, h2, dU, dV = rnd(h1), rnd(h2), rnd(dU), rnd(dV)
     graph = Graph.from_dense(t(counts, cuda))
     groups = Groups(city, prov, cuda)
+    if on_graph is not None:  # (the caller's route assertion, before any kernel runs)
+        on_graph(graph, H, Fd, dtype)
     seed = 5
     tg = [t(x, cuda).requires_grad_(True) for x in (el, er, h1, h2, a3s, a4s)]
     tg[2] = t(h1, cuda, dtype).requires_grad_(True)
@@ -302,11 +304,16 @@ def test_ours_packed_intra_draws_bitwise(cuda, msha, n):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("n", [3000, 140_000])
-def test_ours_deferred_reduce_bitwise(cuda, msha, n, dtype):
+def test_ours_deferred_reduce_bitwise(cuda, msha, monkeypatch, n, dtype):
     """The bipartite forward's v reduce and backward's d_hc / d_er reduce run as extra blocks
     of the intra prep / stage-1 finish launches (msha_bip_defer_reduce): u, v and every
-    gradient equal the separate-launch form's bits.  n = 140k takes the MFMA / mask kernels
-    (>= 131,072 rows), n = 3000 the CSR walk; with dropout and the Ours row coefficients."""
+    gradient equal the separate-launch form's bits, with dropout and the Ours row
+    coefficients.  n = 140k takes the MFMA / mask kernels (>= 131,072 rows) in
+    ours_attention.  n = 3000 runs ours_attention and ours_split_attention (one Function
+    serves both), each under the default cut (mask forward, CSR-walk backward) and with the
+    cut at 0 rows (the large-graph kernels: MFMA forward; backward MFMA for bf16, mask for
+    fp32 with dropout); the route is asserted from msha_bip_route before the runs."""
+    from msha_gnn_amd import _lib
     from msha_gnn_amd import functional as MF
     from msha_gnn_amd.graph import Graph, Groups
 
@@ -325,17 +332,31 @@ def test_ours_deferred_reduce_bitwise(cuda, msha, n, dtype):
     base[2], base[3] = base[2].to(dtype), base[3].to(dtype)
     dU = t(rng.standard_normal((n, H, Fd)), cuda).to(dtype)
     dV = t(rng.standard_normal((m, H, Fd)), cuda).to(dtype)
-    res = []
-    try:
-        for defer in (True, False):
-            MF.BIP_DEFER_REDUCE = defer
-            ins = [x.detach().clone().requires_grad_(True) for x in base]
-            u, v = MF.ours_attention(graph, groups, src, *ins, p=0.3, training=True, seed=5)
-            torch.autograd.backward([u, v], [dU, dV])
-            torch.cuda.synchronize()
-            res.append([u.detach().clone(), v.detach().clone()] + [x.grad.clone() for x in ins])
-    finally:
-        MF.BIP_DEFER_REDUCE = True
-    for a, b in zip(*res):
-        assert torch.equal(a, b)
-    assert (res[0][1] != 0).any() and (res[0][4] != 0).any()
+    bf = dtype == torch.bfloat16
+    monkeypatch.delenv("MSHA_BIP3_BWD32", raising=False)
+    WALK, MASK, MFMA = 1, 2, 3
+    large = (MFMA, MFMA if bf else MASK)
+    if n == 3000:
+        runs = [(fn, cut, want) for fn in (MF.ours_attention, MF.ours_split_attention)
+                for cut, want in ((-1, (MASK, WALK)), (0, large))]
+    else:
+        runs = [(MF.ours_attention, -1, large)]
+    for fn, cut, want in runs:
+        prev = _lib.fn("msha_bip2_bwd_min_rows")(cut)
+        res = []
+        try:
+            code = int(_lib.fn("msha_bip_route")(graph.desc, H, Fd, int(bf), 0.2, 0.3, 0))
+            assert (code % 16, code // 16) == want, (fn.__name__, cut)
+            for defer in (True, False):
+                MF.BIP_DEFER_REDUCE = defer
+                ins = [x.detach().clone().requires_grad_(True) for x in base]
+                u, v = fn(graph, groups, src, *ins, p=0.3, training=True, seed=5)
+                torch.autograd.backward([u, v], [dU, dV])
+                torch.cuda.synchronize()
+                res.append([u.detach().clone(), v.detach().clone()] + [x.grad.clone() for x in ins])
+        finally:
+            MF.BIP_DEFER_REDUCE = True
+            _lib.fn("msha_bip2_bwd_min_rows")(prev)
+        for a, b in zip(*res):
+            assert torch.equal(a, b)
+        assert (res[0][1] != 0).any() and (res[0][4] != 0).any()
