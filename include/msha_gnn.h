@@ -934,6 +934,32 @@ MSHA_API int msha_adam_rows_step(int64_t n, int32_t feat, int32_t dtype, void* p
                                  const int32_t* rows, const int32_t* n_rows, int64_t cap,
                                  const float* vals, double lr, double beta1, double beta2,
                                  double eps, msha_stream_t stream); /* (ABI 16, added) */
+/* The dense update (weight decay included) at the cost of the listed rows, by replaying the
+ * steps a row missed (ABI 16, added).  T = (int)*step is the count of completed steps;
+ * row_step[r] (int32, n entries, 0 for fresh state) is the step after which row r's param,
+ * exp_avg, exp_avg_sq in memory are valid.  For each listed row r (rows[i], i < n_rows[0] <=
+ * cap; rows == NULL: every row, cap == n, n_rows unused) and t = row_step[r] + 1 ...
+ * min(T, row_step[r] + max_steps) the row takes msha_adam_step's update with gradient +0.0
+ * (plus weight_decay * param) and step t's own bias corrections -- the bits the dense step
+ * left at step t; a bf16 row is rounded through bf16 after every replayed step.  With vals
+ * != NULL ((cap, feat) fp32, entry i the gradient of rows[i], or of row i with rows == NULL)
+ * a row that has reached T then takes step T + 1 with its gradient (rounded once to bf16 for
+ * a bf16 table), and a trailing one-thread launch sets *step = T + 1; give max_steps =
+ * INT32_MAX there, or a row further behind than max_steps loses its gradient.  vals == NULL:
+ * catch up only, *step is left alone.  Each row is read and written once per launch and
+ * row_step[r] is set to the step reached; rows that have nothing to do are not read.  After
+ * every row has been caught up (rows == NULL, ceil(T / max_steps) launches) the table and
+ * its moments hold the bits of T msha_adam_step calls on the dense gradients.  One set of
+ * hyperparameters serves all replayed steps: catch every row up before changing them.
+ * rows must be distinct (msha_plan_rows, msha_row_grad_union); an entry outside [0, n) is
+ * skipped.  feat as msha_link_bce_supported; 1 <= cap <= n; max_steps >= 1; no atomics. */
+MSHA_API int msha_adam_rows_replay(int64_t n, int32_t feat, int32_t dtype, void* param,
+                                   void* exp_avg, void* exp_avg_sq, float* step,
+                                   int32_t* row_step, const int32_t* rows,
+                                   const int32_t* n_rows, int64_t cap, const float* vals,
+                                   int32_t max_steps, double lr, double beta1, double beta2,
+                                   double eps, double weight_decay,
+                                   msha_stream_t stream); /* (ABI 16, added) */
 
 /* ---- Projection of a small node table in one workgroup (the recipient side: R15 has 32
  * recipients; Ablation.py:262, :266-267): h = X @ W (M x N, N = heads*feat) with optional

@@ -330,6 +330,9 @@ SIGNATURES = {
     "msha_row_grad_union": (C.c_int, [I64, I32, I32, P, P, P, I64, P, P, SZ, P]),
     "msha_adam_rows_step": (C.c_int, [I64, I32, I32, P, P, P, P, P, P, I64, P, C.c_double,
                                       C.c_double, C.c_double, C.c_double, P]),
+    "msha_adam_rows_replay": (C.c_int, [I64, I32, I32, P, P, P, P, P, P, P, I64, P, I32,
+                                        C.c_double, C.c_double, C.c_double, C.c_double,
+                                        C.c_double, P]),
     # GraphSAGE baseline on sparse adjacency rows (ABI 16, added)
     "msha_sage_supported": (C.c_int, [I32, I32, I32]),
     "msha_sage_workspace_size": (SZ, [I64, I64, I32, I32, I32]),

@@ -278,6 +278,177 @@ __global__ void __launch_bounds__(256) adam_rows_kernel(AdamRows b) {
 
 __global__ void adam_rows_tick_kernel(float* step) { *step = *step + 1.f; }
 
+// ---- lazy Adam that replays the steps a row missed (msha_adam_rows_replay): the dense
+// update, weight decay included, at the cost of the rows a batch names.  Adam is elementwise:
+// a row that no batch named for k steps has, under the dense optimizer, taken k updates with
+// gradient +0.0 (plus wd * p).  row_step[r] records the step after which row r's p, m, v in
+// memory are valid; a lane group that names r reads the row once, applies adam_elem with
+// g = +0.0 for every missed step t with step t's own scalars (adam_scalars(t): the bits the
+// dense kernel derived at step t), then the current step's gradient if there is one, and
+// writes the row once.  bf16 rows pass through bf16 after every replayed step, as the dense
+// kernel's store and reload do.
+//
+// The scalars of a step cost more than a lane's 4 or 8 element updates (a double power by
+// squaring, a divide, a square root), so a block shares them: per pass it finds the span of
+// steps its rows miss (a min / max over the block through shuffles and LDS, no atomics) and
+// walks it in windows of 256 steps, thread k filling step w0 + k's scalars, every lane group
+// reading the ones it needs.  All loop bounds around a barrier are block-uniform.
+struct AdamReplay {
+  void *param, *exp_avg, *exp_avg_sq;
+  float* step;
+  int32_t* row_step;
+  const int32_t *rows, *n_rows;
+  const float* vals;
+  int64_t n, cap;
+  int F, max_steps;
+  double lr, b1, b2, eps, wd;
+};
+
+constexpr int kReplayWindow = 256;  // steps whose scalars a block holds at a time (= block size)
+
+template <bool BF>
+__device__ __forceinline__ void rp_ld(const void* p, int64_t q, float (&x)[BF ? 8 : 4]) {
+  if constexpr (BF) {
+    ad_ld8(p, q, x);
+  } else {
+    const float4 w = reinterpret_cast<const float4*>(p)[q];
+    x[0] = w.x, x[1] = w.y, x[2] = w.z, x[3] = w.w;
+  }
+}
+template <bool BF>
+__device__ __forceinline__ void rp_st(void* p, int64_t q, const float (&x)[BF ? 8 : 4]) {
+  if constexpr (BF)
+    ad_st8(p, q, x);
+  else
+    reinterpret_cast<float4*>(p)[q] = make_float4(x[0], x[1], x[2], x[3]);
+}
+// what a bf16 store and reload leave of a lane's 8 values
+__device__ __forceinline__ void rp_through_bf16(float (&x)[8]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t u = pack_bf16x2(x[2 * k], x[2 * k + 1]);
+    x[2 * k] = __uint_as_float(u << 16);
+    x[2 * k + 1] = __uint_as_float(u & 0xffff0000u);
+  }
+}
+
+template <bool BF>
+__global__ void __launch_bounds__(256) adam_replay_kernel(AdamReplay b) {
+  constexpr int V = BF ? 8 : 4;  // elements in a lane's 16 bytes
+  constexpr int dt = BF ? MSHA_DTYPE_BF16 : MSHA_DTYPE_F32;
+  __shared__ float2 s_win[kReplayWindow];
+  __shared__ int s_lo[4], s_hi[4];
+  const int G = b.F / V;      // lanes per row, a power of two <= 64: a group lies in one wave
+  const int rpb = 256 / G;    // rows of a block per pass
+  int64_t cnt = b.n;
+  if (b.rows != nullptr) {
+    const int64_t c = b.n_rows[0];
+    cnt = c < 0 ? 0 : c > b.cap ? b.cap : c;
+  }
+  int64_t base = (int64_t)blockIdx.x * rpb;
+  if (base >= cnt) return;  // (the whole block)
+  const int T = (int)*b.step;  // completed steps
+  const int lg = (int)threadIdx.x / G, q = (int)threadIdx.x % G;
+  AdamScalars a;
+  a.b1c = (float)(1.0 - b.b1);
+  a.b2c = (float)(1.0 - b.b2);
+  a.b2 = (float)b.b2;
+  a.wd = (float)b.wd;
+  a.eps = (float)b.eps;
+  float2 sc_next = make_float2(0.f, 0.f);  // step T + 1's, for the gradient
+  if (b.vals != nullptr) sc_next = adam_scalars(b.lr, b.b1, b.b2, (float)T + 1.f);
+  // a zero-gradient step leaves an element with m = v = +0 as it is when nothing decays it
+  const bool rest_ok = a.wd == 0.f && a.eps > 0.f;
+  const float4* vals = reinterpret_cast<const float4*>(b.vals);
+  const int64_t stride = (int64_t)gridDim.x * rpb;
+  for (; base < cnt; base += stride) {
+    const int64_t i = base + lg;
+    int64_t r = -1;
+    if (i < cnt) {
+      r = b.rows != nullptr ? (int64_t)b.rows[i] : i;
+      if ((uint64_t)r >= (uint64_t)b.n) r = -1;  // (not a list of this table: no stray access)
+    }
+    int rs = 0, end = 0;
+    bool take = false;
+    if (r >= 0) {
+      rs = b.row_step[r];  // every lane of the group, before lane 0 writes it below
+      const int64_t e = (int64_t)rs + b.max_steps;
+      end = e < (int64_t)T ? (int)e : T;
+      if (end < rs) end = rs;
+      take = b.vals != nullptr && end >= T;
+    }
+    const bool gap = r >= 0 && end > rs;
+    const int64_t qt = r * G + q;
+    float p[V], m[V], v[V];
+    bool replay = false;
+    if (gap || take) {
+      rp_ld<BF>(b.param, qt, p);
+      rp_ld<BF>(b.exp_avg, qt, m);
+      rp_ld<BF>(b.exp_avg_sq, qt, v);
+      replay = gap;
+      if (gap && rest_ok) {
+        bool rest = true;
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+          rest = rest && __float_as_uint(m[k]) == 0u && __float_as_uint(v[k]) == 0u &&
+                 fabsf(p[k]) < __builtin_inff();
+        replay = !rest;
+      }
+    }
+    // the block's span of missed steps
+    int lo = replay ? rs + 1 : 0x7fffffff, hi = replay ? end : 0;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      lo = min(lo, __shfl_xor(lo, o));
+      hi = max(hi, __shfl_xor(hi, o));
+    }
+    __syncthreads();  // the last pass has read s_lo / s_hi
+    if ((threadIdx.x & 63) == 0) s_lo[threadIdx.x >> 6] = lo, s_hi[threadIdx.x >> 6] = hi;
+    __syncthreads();
+    const int blo = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
+    const int bhi = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
+    for (int w0 = blo; w0 <= bhi; w0 += kReplayWindow) {
+      __syncthreads();  // the last window has been read
+      if (w0 + (int)threadIdx.x <= bhi)
+        s_win[threadIdx.x] = adam_scalars(b.lr, b.b1, b.b2, (float)(w0 + (int)threadIdx.x));
+      __syncthreads();
+      if (replay) {
+        const int t1 = min(end, w0 + kReplayWindow - 1);
+        for (int t = max(rs + 1, w0); t <= t1; ++t) {
+          const float2 sc = s_win[t - w0];
+          a.step_size = sc.x;
+          a.bc2_sqrt = sc.y;
+#pragma unroll
+          for (int k = 0; k < V; ++k) adam_elem(a, 0.f, p[k], m[k], v[k]);
+          if constexpr (BF) {
+            rp_through_bf16(p);
+            rp_through_bf16(m);
+            rp_through_bf16(v);
+          }
+        }
+      }
+    }
+    if (take) {  // the row stands at step T: step T + 1 with its gradient row
+      a.step_size = sc_next.x;
+      a.bc2_sqrt = sc_next.y;
+      float g[V];
+#pragma unroll
+      for (int j = 0; j < V / 4; ++j) {
+        const float4 w = vals[(i * b.F + q * V) / 4 + j];
+        g[4 * j] = w.x, g[4 * j + 1] = w.y, g[4 * j + 2] = w.z, g[4 * j + 3] = w.w;
+      }
+#pragma unroll
+      for (int k = 0; k < V; ++k) adam_elem(a, ad_round(dt, g[k]), p[k], m[k], v[k]);
+    }
+    if (replay || take) {
+      rp_st<BF>(b.param, qt, p);
+      rp_st<BF>(b.exp_avg, qt, m);
+      rp_st<BF>(b.exp_avg_sq, qt, v);
+    }
+    if ((gap || take) && q == 0) b.row_step[r] = take ? T + 1 : end;
+  }
+}
+
 }  // namespace msha
 
 using namespace msha;
@@ -351,6 +522,47 @@ extern "C" int msha_adam_rows_step(int64_t n, int32_t feat, int32_t dtype, void*
                      s, b);
   hipLaunchKernelGGL(adam_rows_tick_kernel, dim3(1), dim3(1), 0, s, step);
   return check_launch("adam_rows_step");
+}
+
+extern "C" int msha_adam_rows_replay(int64_t n, int32_t feat, int32_t dtype, void* param,
+                                     void* exp_avg, void* exp_avg_sq, float* step,
+                                     int32_t* row_step, const int32_t* rows,
+                                     const int32_t* n_rows, int64_t cap, const float* vals,
+                                     int32_t max_steps, double lr, double beta1, double beta2,
+                                     double eps, double weight_decay, msha_stream_t stream) {
+  MSHA_ARG_CHECK(n >= 1 && n < ((int64_t)1 << 31) - 1,
+                 "adam_rows_replay: bad sizes (1 <= n < 2^31 - 1)");
+  MSHA_ARG_CHECK(pg_width_ok(feat, dtype),
+                 "adam_rows_replay: unsupported width: feat must be a power of two in [16 B, "
+                 "64 lanes x 16 B] of an fp32 or bf16 table (msha_link_bce_supported)");
+  MSHA_ARG_CHECK(cap >= 1 && cap <= n,
+                 "adam_rows_replay: cap must be in [1, n] (msha_plan_rows)");
+  MSHA_ARG_CHECK(param && exp_avg && exp_avg_sq && step && row_step && (!rows || n_rows),
+                 "adam_rows_replay: null pointer");
+  MSHA_ARG_CHECK(rows != nullptr || cap == n,
+                 "adam_rows_replay: rows == NULL names every row: cap must be n");
+  MSHA_ARG_CHECK(max_steps >= 1, "adam_rows_replay: max_steps must be at least 1");
+  MSHA_ARG_CHECK((((uintptr_t)param | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq |
+                   (uintptr_t)vals) & 15) == 0,
+                 "adam_rows_replay: the table, its moments and vals must be 16-byte aligned");
+  MSHA_ARG_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 &&
+                     weight_decay >= 0.0,
+                 "adam_rows_replay: bad hyperparameters (betas in [0, 1), eps >= 0, "
+                 "weight_decay >= 0)");
+  AdamReplay b{};
+  b.param = param, b.exp_avg = exp_avg, b.exp_avg_sq = exp_avg_sq, b.step = step;
+  b.row_step = row_step, b.rows = rows, b.n_rows = n_rows, b.vals = vals;
+  b.n = n, b.cap = cap, b.F = feat, b.max_steps = max_steps;
+  b.lr = lr, b.b1 = beta1, b.b2 = beta2, b.eps = eps, b.wd = weight_decay;
+  const int lanes = feat * (dtype == MSHA_DTYPE_BF16 ? 2 : 4) / 16;  // per row
+  const dim3 grid(grid_for(cap, 256 / lanes, 1 << 20));
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == MSHA_DTYPE_BF16)
+    hipLaunchKernelGGL(adam_replay_kernel<true>, grid, dim3(256), 0, s, b);
+  else
+    hipLaunchKernelGGL(adam_replay_kernel<false>, grid, dim3(256), 0, s, b);
+  if (vals != nullptr) hipLaunchKernelGGL(adam_rows_tick_kernel, dim3(1), dim3(1), 0, s, step);
+  return check_launch("adam_rows_replay");
 }
 
 extern "C" size_t msha_adam_workspace_size(void) {

@@ -1088,6 +1088,8 @@ def sage_forward(table, src, graph, vals, W1, b1, W2, b2, check=True):
     if check and src.numel():
         src, _ = check_pair_indices(src, src, table.shape[0])
     vals = vals.contiguous()
+    if src.numel():  # (the backward lists the batch's rows itself: too late for the read)
+        _replay_catch_up(table, None, lambda: pair_plan(src, src, table.shape[0]))
     if torch.is_grad_enabled() and any(t.requires_grad for t in (table, W1, b1, W2, b2)):
         return _Sage.apply(table, W1, b1, W2, b2, src, graph, vals)
     tb = table.detach()
@@ -1851,6 +1853,25 @@ def _stash_rows(leaf, plan, launch):
     launch(rows.data_ptr(), n_rows.data_ptr(), rows.numel(), vals.data_ptr())
 
 
+def _replay_catch_up(h, plan, make_plan):
+    """Before a loss reads the table ``h``: when ``h`` is registered with
+    ``optim.Adam.fuse_row_grad(replay=True)``, the rows the loss is about to read are
+    brought up to the present step (``Adam.catch_up``: one launch, nothing read back), in
+    grad mode or not.  The rows are those of ``plan``, or of ``make_plan()``, built here.
+    Returns the plan (``plan`` unchanged for any other ``h``)."""
+    if not getattr(h, "_msha_row_replay", False):
+        return plan
+    from .optim import row_optimizer_of
+
+    opt = row_optimizer_of(h)
+    if opt is None:
+        return plan
+    if plan is None:
+        plan = make_plan()
+    opt.catch_up(h, plan)
+    return plan
+
+
 def row_grad_union(grads):
     """The sum of 2 to 4 ``RowGrad``s of one table as one ``RowGrad`` (``msha_row_grad_union``):
     ``rows`` the ascending union (capacity ``min(n, sum of the capacities)``), ``values[i]`` the
@@ -2070,6 +2091,7 @@ def link_bce_loss(h, src, dst, target, weight=None, plan=None, return_logits=Fal
     target = target.detach().to(torch.float32).contiguous()
     weight = weight.detach().to(torch.float32).contiguous() if weight is not None else None
     src, dst = src.contiguous(), dst.contiguous()
+    plan = _replay_catch_up(h, plan, lambda: pair_plan(src, dst, h.shape[0]))
     if plan is None and h.requires_grad and torch.is_grad_enabled():
         plan = pair_plan(src, dst, h.shape[0])  # only a backward reads it
     loss, z, _ = _LinkBCE.apply(h, src, dst, target, weight, plan)
@@ -2214,6 +2236,7 @@ def link_mlp_loss(h, src, dst, W, b, *, label=None, teacher_out=None, w_label=1.
         teacher_out = teacher_out.detach().to(torch.float32).contiguous()
     if seed is None:
         seed = new_seed() if p > 0 else 0
+    plan = _replay_catch_up(h, plan, lambda: pair_plan(src, dst, h.shape[0]))
     if plan is None and h.requires_grad and torch.is_grad_enabled():
         plan = pair_plan(src, dst, h.shape[0])  # only a backward reads it
     loss, out, terms, _ = _LinkMLP.apply(h, W, b, src, dst, label, teacher_out, float(w_label),
@@ -2398,6 +2421,7 @@ def link_distill_loss(h, anchors, context, *, teacher_logits=None, teacher_table
     tl = (teacher_logits.detach().to(torch.float32).contiguous()
           if teacher_logits is not None else None)
     th = teacher_table.detach() if teacher_table is not None else None
+    plan = _replay_catch_up(h, plan, lambda: context_plan(anchors, context, h.shape[0]))
     if plan is None and h.requires_grad and torch.is_grad_enabled():
         plan = context_plan(anchors, context, h.shape[0])  # only a backward reads it
     loss, terms, logits, _ = _LinkDistill.apply(h, anchors, context, tl, th, margin, tau,
@@ -2503,6 +2527,12 @@ def link_match_loss(h, rows, teacher_table, *, return_rows=False):
     _check_same_device("link_match_loss", h, rows, t)
     _lib.require_cuda(h)
     rows = rows.contiguous() if rows is not None else None
+    if rows is not None:
+        # (the backward lists the rows from its histogram: too late for the read; the
+        # (rows, rows) plan gives the distinct rows now)
+        _replay_catch_up(h, None, lambda: pair_plan(rows, rows, h.shape[0]))
+    else:
+        _replay_catch_up(h, None, lambda: None)  # every row is read: the flush
     loss, cos_rows, count, _ = _LinkMatch.apply(h, rows, t.detach())
     return (loss, cos_rows, count) if return_rows else loss
 

@@ -25,6 +25,16 @@ backward hands this optimizer the gradient of the rows the batch touches
 other rows neither read nor written.  With ``accumulate=True`` up to four such gradients of
 one table (LLP's label + matching + distillation terms) are summed before the step
 (``msha_row_grad_union``).  ``state_dict`` is unchanged.
+
+``fuse_row_grad(param, replay=True)``: the same row path with the *dense* optimizer's
+trajectory, weight decay included (``msha_adam_rows_replay``).  The state gains ``row_step``,
+one int32 per row: the step after which the row in memory is valid.  A row that no batch
+names falls behind; the steps it missed (zero gradient plus ``weight_decay * p``) are replayed
+in registers when the row is next read or stepped, with each step's own bias corrections, so
+after ``catch_up(param)`` the table and both moments hold the bits of the unregistered run.
+The five losses above catch up the rows they read; every other reader of the table
+(``score_pairs``, ``topk_inner``, ``rank_inner``, indexing, a view, a cast, a checkpoint for
+another optimizer) calls ``opt.catch_up(table)`` first.
 """
 from __future__ import annotations
 
@@ -37,6 +47,12 @@ from . import _lib
 
 _DT = {torch.float32: 0, torch.bfloat16: 1}
 MAX_ROW_GRADS = _lib.MAX_ROW_LISTS  # pending row gradients of a fuse_row_grad(accumulate=True) table
+# Replayed steps per row in one launch of catch_up(param)'s flush over the whole table: a
+# launch is bounded by n * F * FLUSH_CHUNK element updates (2M x 128 rows: 2.7e11, a fraction
+# of a second), and a flush after T steps takes ceil(T / FLUSH_CHUNK) launches.  Four of the
+# kernel's 256-step scalar windows.
+FLUSH_CHUNK = 1024
+_ALL_STEPS = 2 ** 31 - 1  # max_steps of a launch that must bring its rows to the present
 
 
 class Adam(torch.optim.Optimizer):
@@ -128,8 +144,27 @@ class Adam(torch.optim.Optimizer):
                                           "group (loaded state_dict?)")
 
     def load_state_dict(self, state_dict):
+        # torch casts every state tensor but 'step' to the parameter's dtype; a replay
+        # table's row_step is an int32 record (bf16 would lose it past 256 steps): it goes
+        # round torch's loader
+        ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        params = [p for g in self.param_groups for p in g["params"]]
+        kept = {}
+        if len(ids) == len(params):  # (else torch raises below)
+            kept = {i: st["row_step"] for i, st in state_dict["state"].items()
+                    if isinstance(st, dict) and "row_step" in st}
+        if kept:
+            state_dict = dict(state_dict, state={
+                i: ({k: v for k, v in st.items() if k != "row_step"} if i in kept else st)
+                for i, st in state_dict["state"].items()})
         super().load_state_dict(state_dict)
         self._check_groups()
+        for i, p in zip(ids, params):
+            if i in kept:
+                self.state[p]["row_step"] = torch.as_tensor(kept[i]).to(
+                    device=p.device, dtype=torch.int32, copy=True)
+            if getattr(p, "_msha_row_replay", False):
+                p._msha_replay_hp = None  # the loaded group's values: those of its last launch
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -142,7 +177,9 @@ class Adam(torch.optim.Optimizer):
             by_dev = {}
             for p in group["params"]:
                 if row_optimizer_of(p) is self:
-                    self._check_row_group(group)
+                    replay = getattr(p, "_msha_row_replay", False)
+                    if not replay:
+                        self._check_row_group(group)
                     rg = self.row_grad_of(p)  # several pending: merged once
                     if rg is not None:  # the touched rows' gradient: a lazy step over them
                         if p.grad is not None:
@@ -151,8 +188,17 @@ class Adam(torch.optim.Optimizer):
                                 "and a .grad (it has another consumer besides its link loss): "
                                 "do not register it")
                         _drop_row_grads(p)
-                        self._rows_step(group, p, rg)
+                        if replay:
+                            self._replay_step(group, p, rg)
+                        else:
+                            self._rows_step(group, p, rg)
                         continue
+                    if replay and (p.grad is not None
+                                   or getattr(p, "_msha_dropout_grad", None) is not None):
+                        # a dense step of a replay table (a view or a cast of it was
+                        # trained): every row is brought up to date first and takes the step
+                        self.catch_up(p)
+                        self.state[p]["row_step"].add_(1)
                 stash = getattr(p, "_msha_dropout_grad", None)
                 if stash is not None:  # fused: the dropout's output gradient + its mask
                     if p.grad is not None:
@@ -193,7 +239,7 @@ class Adam(torch.optim.Optimizer):
                              "parameter group (L2 decay makes the gradient dense; this "
                              "optimizer has no decoupled decay)")
 
-    def fuse_row_grad(self, param, accumulate=False):
+    def fuse_row_grad(self, param, accumulate=False, replay=False):
         """Train the 2-D leaf table ``param`` at the cost of the rows a batch touches;
         returns ``param``.  ``functional.link_bce_loss``, ``link_distill_loss``,
         ``link_mlp_loss``, ``link_match_loss`` (with ``rows``) and ``sage_forward`` called on
@@ -213,14 +259,34 @@ class Adam(torch.optim.Optimizer):
         encoder's output of the table takes the dense path as before.  When a batch names
         every row (P in the millions on a 100k-row table) the list adds work and nothing is
         saved: the registered step may then be slower than the dense one
-        (profiles/row_adam_ab)."""
+        (profiles/row_adam_ab).
+
+        ``replay=True``: the dense optimizer's trajectory instead of the frozen-moment one,
+        and the group's ``weight_decay`` may be non-zero (SGAE.py:79, train.py:207 train with
+        5e-4).  ``step()`` runs ``msha_adam_rows_replay``: a stepped row first takes the
+        steps it missed -- zero gradient plus ``weight_decay * p``, each with its own bias
+        corrections -- and then this step, between one read and one write of the row.  The
+        state gains ``row_step`` (int32, one per row, part of ``state_dict()``; a loaded
+        state without it means every row is current).  Rows that no batch names are stale in
+        memory until they are next read: the five losses above catch up the rows they read
+        (``catch_up(param, plan)``, one more launch, capturable); any other reader calls
+        ``catch_up(param)`` first.  After it the table and both moments hold the bits of the
+        unregistered run.  All replayed steps use one set of (lr, betas, eps, weight_decay):
+        when the group's values change, the next ``step()`` / ``catch_up()`` first brings
+        every row up to date under the old ones (one pass over the table and one readback of
+        the step count), so a scheduler that changes lr every step makes this path dense."""
         group = self._group_of(param)  # must be ours
         if param.dim() != 2 or not param.is_leaf:
             raise ValueError("msha Adam: fuse_row_grad takes a 2-D leaf table, got "
                              f"{tuple(param.shape)}")
-        self._check_row_group(group)
+        if not replay:
+            self._check_row_group(group)
         param._msha_row_adam = weakref.ref(self)
         param._msha_row_accumulate = bool(accumulate)
+        param._msha_row_replay = bool(replay)
+        param._msha_replay_hp = None
+        if replay:
+            self._replay_state(param)
         return param
 
     def stash_row_grad(self, param, row_grad):
@@ -266,6 +332,104 @@ class Adam(torch.optim.Optimizer):
                   rg.rows.data_ptr(), rg.n_rows.data_ptr(), rg.rows.numel(),
                   rg.values.data_ptr(), float(group["lr"]), float(b1), float(b2),
                   float(group["eps"]), _lib.stream_handle(p.device))
+
+    # ------------------------------------------ row-sparse updates, missed steps replayed
+    def _replay_state(self, p):
+        """The state of a replay table with its ``row_step``; without one (fresh state, or
+        a loaded state_dict that has none) every row is current: the step count."""
+        st = self._state_of(p)
+        rs = st.get("row_step")
+        n = p.shape[0]
+        if rs is None:
+            st["row_step"] = st["step"].to(torch.int32).expand(n).contiguous()
+        elif (rs.dtype != torch.int32 or rs.device != p.device or rs.shape != (n,)
+              or not rs.is_contiguous()):
+            if rs.numel() != n:
+                raise ValueError(f"msha Adam: row_step has {rs.numel()} entries, the table "
+                                 f"{n} rows")
+            st["row_step"] = rs.to(device=p.device, dtype=torch.int32).reshape(n).contiguous()
+        return st
+
+    @staticmethod
+    def _hyper(group):
+        b1, b2 = group["betas"]
+        return (float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                float(group["weight_decay"]))
+
+    def _replay_launch(self, p, hyper, rows, n_rows, cap, vals, max_steps):
+        if p.dtype not in _DT or not p.is_contiguous():
+            raise TypeError("msha Adam: a fuse_row_grad table is a contiguous fp32 / bf16 "
+                            f"parameter (got {p.dtype})")
+        st = self._replay_state(p)
+        _lib.call("msha_adam_rows_replay", p.shape[0], p.shape[1], _DT[p.dtype], p.data_ptr(),
+                  st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr(),
+                  st["row_step"].data_ptr(), _lib.ptr(rows), _lib.ptr(n_rows), cap,
+                  _lib.ptr(vals), int(max_steps), *hyper, _lib.stream_handle(p.device))
+
+    def _flush(self, p, hyper, chunk=None):
+        """Every row of ``p`` up to the present under ``hyper``: ceil(T / chunk) launches of
+        at most ``chunk`` replayed steps per row (one readback, of the step count)."""
+        chunk = FLUSH_CHUNK if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"msha Adam: chunk must be at least 1, got {chunk}")
+        T = int(self._replay_state(p)["step"].item())
+        for _ in range(-(-T // chunk)):
+            self._replay_launch(p, hyper, None, None, p.shape[0], None, min(chunk, _ALL_STEPS))
+
+    def _replay_hyper(self, group, p):
+        """The group's hyperparameters; when they differ from those of the table's last
+        launch, every row is first brought up to date under the old ones."""
+        hyper = self._hyper(group)
+        last = getattr(p, "_msha_replay_hp", None)
+        if last is not None and last != hyper:
+            self._flush(p, last)
+        p._msha_replay_hp = hyper
+        return hyper
+
+    def _replay_step(self, group, p, rg):
+        _lib.require_cuda(p, rg.values)
+        # (a row behind by any number of steps must reach the present to take its gradient)
+        self._replay_launch(p, self._replay_hyper(group, p), rg.rows, rg.n_rows,
+                            rg.rows.numel(), rg.values, _ALL_STEPS)
+
+    def _replay_table(self, param):
+        if row_optimizer_of(param) is not self or not getattr(param, "_msha_row_replay", False):
+            raise ValueError("msha Adam: not a table registered with "
+                             "fuse_row_grad(replay=True) on this optimizer")
+        return self._group_of(param)
+
+    def catch_up(self, param, rows=None, chunk=None):
+        """Bring rows of a ``fuse_row_grad(replay=True)`` table up to the present step, so
+        that they can be read.  ``rows``: a ``functional.PairPlan`` (its ``plan_rows``) or a
+        ``(rows, n_rows)`` pair of distinct int32 row ids and their device count -- one
+        launch, nothing read back, capturable.  ``rows=None``: every row, the flush before
+        evaluation, ``topk_inner`` / ``rank_inner`` / ``score_pairs``, indexing, or a
+        checkpoint meant for another optimizer; it reads the step count T back once and
+        issues ceil(T / chunk) launches of at most ``chunk`` (default ``FLUSH_CHUNK`` = 1024)
+        replayed steps per row, so no single launch is unbounded; not meant to be captured.
+        Rows that are current are not touched; calling it twice changes nothing."""
+        group = self._replay_table(param)
+        _lib.require_cuda(param)
+        hyper = self._replay_hyper(group, param)
+        if rows is None:
+            self._flush(param, hyper, chunk)
+            return
+        from .functional import PairPlan, plan_rows
+
+        rows, n_rows = plan_rows(rows) if isinstance(rows, PairPlan) else rows
+        if rows.dtype != torch.int32 or n_rows.dtype != torch.int32:
+            raise TypeError("msha Adam: catch_up takes int32 rows and an int32 device count "
+                            "(plan_rows)")
+        _lib.require_cuda(rows, n_rows)
+        if rows.numel():
+            self._replay_launch(param, hyper, rows, n_rows, rows.numel(), None, _ALL_STEPS)
+
+    def stale_rows(self, param):
+        """The number of rows of a replay table that are behind the step count (a device
+        int64 scalar, a plain torch expression)."""
+        self._replay_table(param)
+        st = self._replay_state(param)
+        return (st["row_step"] < st["step"].to(torch.int32)).sum()
 
     # ---------------------------------------------- fused dropout-backward updates
     def fuse_dropout_grad(self, param):
