@@ -1072,6 +1072,126 @@ __global__ void __launch_bounds__(256) bwd_cols_kernel(
 // loop is branch-free and its waits exact; two slot groups per trip, each group's
 // CSC rows loaded two groups ahead into the register it just consumed.
 // Needs every table below 2 GiB (msha_edge_attention_bwd_fused checks).
+
+// What a wave of the head-per-lane column pass carries from column to column (ii) and what
+// one column gives (acc, xacc).
+template <typename T, int NV>
+struct ColsEh {
+  int32_t ii[COLS_NG];  // CSC rows of the lane's slot in the next COLS_NG slot groups
+  Pk<T> acc[NV];        // sum attd_ij dU_i[h] over the column's slots, slot lanes reduced
+  float xacc;           // sum de_ij, slot lanes reduced
+};
+
+// One column (slots [s0, s1), or one chunk of a long column) of the head-per-lane column
+// pass, from "hc_j[h] (hcv) and er_j (er_tab) are known" to "acc and xacc are reduced": the
+// only copy of this code, inlined into bwd_cols_eh_kernel and bwd_cols_wgrad_kernel.  The CSC
+// rows of [ns0, ns1), the wave's next column (empty: none), are loaded at the column's end.
+template <int H, int F, typename T, bool RSC>
+__device__ __forceinline__ ColsEh<T, Geo<H, F, T>::QH> cols_eh_column(
+    ColsEh<T, Geo<H, F, T>::QH> st, int e_s, int h_s, int32_t s0, int32_t s1, int32_t ns0,
+    int32_t ns1, const Pk<T> (&hcv)[Geo<H, F, T>::QH], float er_tab, const float* __restrict__ ar,
+    rsrc_t r_row, rsrc_t r_eid, rsrc_t r_flag, rsrc_t r_rec, rsrc_t r_dU, rsrc_t r_de,
+    bool need_eid, bool slot_de, float slope, Dropout dp) {
+  using G = Geo<H, F, T>;
+  constexpr int NV = G::QH;  // 16-B pieces per head
+  constexpr int NG = COLS_NG;
+  const uint32_t h_off = h_s * F * sizeof(T);
+  int32_t(&ii)[NG] = st.ii;
+  Pk<T>(&acc)[NV] = st.acc;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) acc[k] = pk_zero<T>();
+  float xacc = 0.f;
+  // one trip = COLS_NG slot groups: every group's loads leave before the first
+  // group's compute and de store (the compiler may not hoist a buffer load above a
+  // buffer store), then the groups are consumed in slot order
+  for (int32_t cs = s0; cs < s1; cs += NG * G::CE) {
+    Pk<T> dUv[NG][NV];
+    int32_t eid[NG];
+    float r_el[NG], r_lse[NG], Dsi[NG];
+    uint32_t vflag[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const bool valid = cs + g * G::CE + e_s < s1;
+      const uint32_t row_off = valid ? (uint32_t)ii[g] * (G::D * sizeof(T)) + h_off : kOOB;
+#pragma unroll
+      for (int k = 0; k < NV; ++k)
+        dUv[g][k] = pk_load_buf(r_dU, row_off + (valid ? k * 16u : 0u), (T*)nullptr);
+      eid[g] = buf_i32(r_eid, valid && need_eid ? (uint32_t)(cs + g * G::CE + e_s) * 4u : kOOB);
+      const uint32_t rec_off = valid ? (uint32_t)ii[g] * (4u * rec_stride(H)) + h_s * 4u : kOOB;
+      r_el[g] = buf_f32(r_rec, rec_off);
+      r_lse[g] = buf_f32(r_rec, valid ? rec_off + 4u * H : kOOB);
+      Dsi[g] = buf_f32(r_rec, valid ? rec_off + 8u * H : kOOB);
+      if constexpr (rec_has_flag(H))
+        vflag[g] = __float_as_uint(buf_f32(r_rec, valid ? rec_off - h_s * 4u + 12u * H : kOOB));
+      else
+        vflag[g] = buf_u8(r_flag, valid ? (uint32_t)ii[g] : kOOB);
+    }
+    // CSC rows of the next trip
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int32_t a = cs + (NG + g) * G::CE + e_s;
+      ii[g] = buf_i32(r_row, a < s1 ? (uint32_t)a * 4u : kOOB);
+    }
+    // er_j: from hc_j in the row-score forward's order when a_r is given, recomputed
+    // per trip AFTER the trip's loads are in flight (computed before the loop, the wait
+    // for hc_j / a_r put one memory latency in front of every chunk's loads); the empty
+    // asm keeps it from being hoisted back out of the loop
+    float erh = er_tab;
+    if (RSC) {
+      Pk<T> hv[NV];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        hv[k] = hcv[k];
+#pragma unroll
+        for (int v = 0; v < G::V; ++v) asm volatile("" : "+v"(hv[k].v[v]));
+      }
+      erh = head_score<NV>(hv, ar + h_s * F);
+    }
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int32_t slot = cs + g * G::CE + e_s;
+      const bool valid = slot < s1;
+      const bool virt = vflag[g] != 0;
+      const float pre = r_el[g] + erh;
+      const float sv = virt ? 0.f : lrelu(pre, slope);
+      const float att = __expf(sv - r_lse[g]);
+      const float dropf = dropout_factor(dp, (uint64_t)eid[g] * H + h_s);
+      const float wv = valid ? att * dropf : 0.f;
+      // dU_i[h] . hc_j[h] in group_sum's order over the head's pieces
+      float d[NV];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        d[k] = pk_dot(dUv[g][k], hcv[k]);
+        acc[k] = pk_fma(wv, dUv[g][k], acc[k]);
+      }
+#pragma unroll
+      for (int o = 1; o < NV; o <<= 1)
+#pragma unroll
+        for (int k = 0; k < NV; k += 2 * o) d[k] = d[k] + d[k + o];
+      const float ds = att * (d[0] * dropf - Dsi[g]);
+      const float dev = virt ? 0.f : ds * (pre > 0.f ? 1.f : slope);
+#ifndef DIAG_NO_DE
+      const uint32_t at = slot_de ? (uint32_t)slot : (uint32_t)eid[g];
+      buf_store_f32(r_de, valid ? at * (4u * H) + h_s * 4u : kOOB, dev);
+#endif
+      xacc += valid ? dev : 0.f;
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int32_t a = ns0 + g * G::CE + e_s;
+    ii[g] = buf_i32(r_row, a < ns1 ? (uint32_t)a * 4u : kOOB);
+  }
+#pragma unroll
+  for (int k = 0; k < NV; ++k)
+#pragma unroll
+    for (int o = H; o < 64; o <<= 1) acc[k] = pk_xor_add(acc[k], o);
+  st.xacc = wave_xor_sum<H>(xacc);
+  return st;
+}
+
+// The head-per-lane column pass over the chunk plan: a wave takes chunks wave, wave + nwaves,
+// ... and reads the next chunk's plan entry during this one.
 template <int H, int F, typename T, bool RSC = false>
 __global__ void __launch_bounds__(256) bwd_cols_eh_kernel(
     const int32_t* __restrict__ chunk_col, const int32_t* __restrict__ chunk_start,
@@ -1095,7 +1215,6 @@ __global__ void __launch_bounds__(256) bwd_cols_eh_kernel(
   const rsrc_t r_rec = make_rsrc(rec, (uint32_t)(n_rows * 4 * rec_stride(H)));
   const rsrc_t r_dU = make_rsrc(dU, (uint32_t)(n_rows * G::D * sizeof(T)));
   const rsrc_t r_de = make_rsrc(de, (uint32_t)(n_edges * 4 * H));
-  const uint32_t h_off = h_s * F * sizeof(T);
   // the CSR edge id serves the dropout stream and an edge-ordered de only: otherwise its
   // load stays off the memory system (kOOB)
   const bool need_eid = dp.active || (de != nullptr && !slot_de);
@@ -1103,11 +1222,11 @@ __global__ void __launch_bounds__(256) bwd_cols_eh_kernel(
   int64_t c = wave;
   if (c >= n_chunks) return;
   int32_t jc = chunk_col[c], s0 = chunk_start[c], s1 = chunk_end[c];
-  int32_t ii[NG];
+  ColsEh<T, NV> st;
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     const int32_t a = s0 + g * G::CE + e_s;
-    ii[g] = buf_i32(r_row, a < s1 ? (uint32_t)a * 4u : kOOB);
+    st.ii[g] = buf_i32(r_row, a < s1 ? (uint32_t)a * 4u : kOOB);
   }
   while (true) {
     const int64_t nc = c + nwaves;
@@ -1116,115 +1235,29 @@ __global__ void __launch_bounds__(256) bwd_cols_eh_kernel(
     const int32_t ns0 = has_next ? chunk_start[nc] : 0;
     const int32_t ns1 = has_next ? chunk_end[nc] : 0;
     const bool whole = s0 == colptr[jc] && s1 == colptr[jc + 1];
-    Pk<T> hcv[NV], acc[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      hcv[k] = pk_load(hc + (int64_t)jc * G::D + h_s * F + G::V * k);
-      acc[k] = pk_zero<T>();
-    }
-    const float er_tab = RSC ? 0.f : er[(int64_t)jc * H + h_s];
-    float xacc = 0.f;
-    // one trip = COLS_NG slot groups: every group's loads leave before the first
-    // group's compute and de store (the compiler may not hoist a buffer load above a
-    // buffer store), then the groups are consumed in slot order
-    for (int32_t cs = s0; cs < s1; cs += NG * G::CE) {
-      Pk<T> dUv[NG][NV];
-      int32_t eid[NG];
-      float r_el[NG], r_lse[NG], Dsi[NG];
-      uint32_t vflag[NG];
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const bool valid = cs + g * G::CE + e_s < s1;
-        const uint32_t row_off = valid ? (uint32_t)ii[g] * (G::D * sizeof(T)) + h_off : kOOB;
-#pragma unroll
-        for (int k = 0; k < NV; ++k)
-          dUv[g][k] = pk_load_buf(r_dU, row_off + (valid ? k * 16u : 0u), (T*)nullptr);
-        eid[g] = buf_i32(r_eid, valid && need_eid ? (uint32_t)(cs + g * G::CE + e_s) * 4u : kOOB);
-        const uint32_t rec_off = valid ? (uint32_t)ii[g] * (4u * rec_stride(H)) + h_s * 4u : kOOB;
-        r_el[g] = buf_f32(r_rec, rec_off);
-        r_lse[g] = buf_f32(r_rec, valid ? rec_off + 4u * H : kOOB);
-        Dsi[g] = buf_f32(r_rec, valid ? rec_off + 8u * H : kOOB);
-        if constexpr (rec_has_flag(H))
-          vflag[g] = __float_as_uint(buf_f32(r_rec, valid ? rec_off - h_s * 4u + 12u * H : kOOB));
-        else
-          vflag[g] = buf_u8(r_flag, valid ? (uint32_t)ii[g] : kOOB);
-      }
-      // CSC rows of the next trip
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const int32_t a = cs + (NG + g) * G::CE + e_s;
-        ii[g] = buf_i32(r_row, a < s1 ? (uint32_t)a * 4u : kOOB);
-      }
-      // er_j: from hc_j in the row-score forward's order when a_r is given, recomputed
-      // per trip AFTER the trip's loads are in flight (computed before the loop, the wait
-      // for hc_j / a_r put one memory latency in front of every chunk's loads); the empty
-      // asm keeps it from being hoisted back out of the loop
-      float erh = er_tab;
-      if (RSC) {
-        Pk<T> hv[NV];
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-          hv[k] = hcv[k];
-#pragma unroll
-          for (int v = 0; v < G::V; ++v) asm volatile("" : "+v"(hv[k].v[v]));
-        }
-        erh = head_score<NV>(hv, ar + h_s * F);
-      }
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const int32_t slot = cs + g * G::CE + e_s;
-        const bool valid = slot < s1;
-        const bool virt = vflag[g] != 0;
-        const float pre = r_el[g] + erh;
-        const float sv = virt ? 0.f : lrelu(pre, slope);
-        const float att = __expf(sv - r_lse[g]);
-        const float dropf = dropout_factor(dp, (uint64_t)eid[g] * H + h_s);
-        const float wv = valid ? att * dropf : 0.f;
-        // dU_i[h] . hc_j[h] in group_sum's order over the head's pieces
-        float d[NV];
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-          d[k] = pk_dot(dUv[g][k], hcv[k]);
-          acc[k] = pk_fma(wv, dUv[g][k], acc[k]);
-        }
-#pragma unroll
-        for (int o = 1; o < NV; o <<= 1)
-#pragma unroll
-          for (int k = 0; k < NV; k += 2 * o) d[k] = d[k] + d[k + o];
-        const float ds = att * (d[0] * dropf - Dsi[g]);
-        const float dev = virt ? 0.f : ds * (pre > 0.f ? 1.f : slope);
-#ifndef DIAG_NO_DE
-        const uint32_t at = slot_de ? (uint32_t)slot : (uint32_t)eid[g];
-        buf_store_f32(r_de, valid ? at * (4u * H) + h_s * 4u : kOOB, dev);
-#endif
-        xacc += valid ? dev : 0.f;
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int32_t a = ns0 + g * G::CE + e_s;
-      ii[g] = buf_i32(r_row, a < ns1 ? (uint32_t)a * 4u : kOOB);
-    }
+    Pk<T> hcv[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k)
-#pragma unroll
-      for (int o = H; o < 64; o <<= 1) acc[k] = pk_xor_add(acc[k], o);
+      hcv[k] = pk_load(hc + (int64_t)jc * G::D + h_s * F + G::V * k);
+    const float er_tab = RSC ? 0.f : er[(int64_t)jc * H + h_s];
+    st = cols_eh_column<H, F, T, RSC>(st, e_s, h_s, s0, s1, ns0, ns1, hcv, er_tab, ar, r_row,
+                                      r_eid, r_flag, r_rec, r_dU, r_de, need_eid, slot_de, slope,
+                                      dp);
     if (e_s == 0) {
 #pragma unroll
       for (int k = 0; k < NV; ++k) {
         if (whole) {
-          pk_store(d_hc + (int64_t)jc * G::D + h_s * F + G::V * k, acc[k]);
+          pk_store(d_hc + (int64_t)jc * G::D + h_s * F + G::V * k, st.acc[k]);
         } else {
           float* dst = part + c * G::D + h_s * F + G::V * k;
 #pragma unroll
           for (int v = 0; v < G::V; v += 4)
-            *reinterpret_cast<float4*>(dst + v) =
-                make_float4(acc[k].v[v], acc[k].v[v + 1], acc[k].v[v + 2], acc[k].v[v + 3]);
+            *reinterpret_cast<float4*>(dst + v) = make_float4(
+                st.acc[k].v[v], st.acc[k].v[v + 1], st.acc[k].v[v + 2], st.acc[k].v[v + 3]);
         }
       }
     }
-    xacc = wave_xor_sum<H>(xacc);
-    if (lane < H) (whole ? d_er + (int64_t)jc * H : part_x + c * H)[lane] = xacc;
+    if (lane < H) (whole ? d_er + (int64_t)jc * H : part_x + c * H)[lane] = st.xacc;
     if (!has_next) break;
     c = nc;
     jc = njc;
@@ -1239,8 +1272,8 @@ __global__ void __launch_bounds__(256) bwd_cols_eh_kernel(
 // what this pass produces for column j and the d_el the row statistics wrote before it.
 // Persistent grid: block b owns columns [cut[b], cut[b+1]) (col_ranges.h) and walks them in
 // tiles of kFwTile columns.  Block = 12 gather waves + 4 matrix waves (one per SIMD).
-// Gather wave w takes columns w, w + 12, ... of a tile with bwd_cols_eh_kernel's per-column
-// code (same loads, same operation order: d_hc, d_er and de are the same bits).  Next to
+// Gather wave w takes columns w, w + 12, ... of a tile and runs cols_eh_column on each, the
+// function bwd_cols_eh_kernel runs on a chunk: d_hc and d_er are the plain pass's.  Next to
 // hc_j it loads X_j and h_j (8 bytes a lane), and at the column's end it parks X_j and D'_j
 // (wgrad_kernel's order: fmaf(e2, a2, fmaf(e1, a1, d))) in one of two LDS tiles and adds
 // d_el_j h_j, d_er_j h_j to its score-vector sums.  One block barrier per tile; between two
@@ -1367,7 +1400,6 @@ __global__ void __launch_bounds__(64 * kFwWaves) bwd_cols_wgrad_kernel(
   const rsrc_t r_rec = make_rsrc(rec, (uint32_t)(n_rows * 4 * rec_stride(H)));
   const rsrc_t r_dU = make_rsrc(dU, (uint32_t)(n_rows * G::D * sizeof(T)));
   const rsrc_t r_de = make_rsrc(de, (uint32_t)(n_edges * 4 * H));
-  const uint32_t h_off = h_s * F * sizeof(T);
   const bool need_eid = dp.active || (de != nullptr && !slot_de);
   const int c0 = cut[blockIdx.x], c1 = cut[blockIdx.x + 1];
 
@@ -1383,14 +1415,14 @@ __global__ void __launch_bounds__(64 * kFwWaves) bwd_cols_wgrad_kernel(
   float2 cs1 = make_float2(0.f, 0.f), cs2 = cs1;
 
   // the wave's columns in order: slot w + 12 r of tile t is column c0 + t kFwTile + slot
-  int32_t ii[NG];
+  ColsEh<T, NV> st;
   {
     const int32_t jf = c0 + w;
     const int32_t s0f = jf < c1 ? colptr[jf] : 0, s1f = jf < c1 ? colptr[jf + 1] : 0;
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
       const int32_t a = s0f + g * G::CE + e_s;
-      ii[g] = buf_i32(r_row, a < s1f ? (uint32_t)a * 4u : kOOB);
+      st.ii[g] = buf_i32(r_row, a < s1f ? (uint32_t)a * 4u : kOOB);
     }
   }
   int tile = 0;
@@ -1411,91 +1443,26 @@ __global__ void __launch_bounds__(64 * kFwWaves) bwd_cols_wgrad_kernel(
       const int32_t s0 = colptr[jc], s1 = colptr[jc + 1];
       const int32_t ns0 = has_next ? colptr[njc] : 0;
       const int32_t ns1 = has_next ? colptr[njc + 1] : 0;
-      Pk<T> hcv[NV], acc[NV];
+      Pk<T> hcv[NV];
 #pragma unroll
-      for (int k = 0; k < NV; ++k) {
+      for (int k = 0; k < NV; ++k)
         hcv[k] = pk_load(hc + (int64_t)jc * G::D + h_s * F + G::V * k);
-        acc[k] = pk_zero<T>();
-      }
       const float er_tab = er[(int64_t)jc * H + h_s];
       const float2 xv = *reinterpret_cast<const float2*>(X + (int64_t)jc * ldx + n2);
       const float2 hv2 = *reinterpret_cast<const float2*>(hc + (int64_t)jc * G::D + n2);
       const float e1 = d_el[(int64_t)jc * H + hh];
-      float xacc = 0.f;
-      for (int32_t cs = s0; cs < s1; cs += NG * G::CE) {
-        Pk<T> dUv[NG][NV];
-        int32_t eid[NG];
-        float r_el[NG], r_lse[NG], Dsi[NG];
-        uint32_t vflag[NG];
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-          const bool valid = cs + g * G::CE + e_s < s1;
-          const uint32_t row_off = valid ? (uint32_t)ii[g] * (G::D * sizeof(T)) + h_off : kOOB;
-#pragma unroll
-          for (int k = 0; k < NV; ++k)
-            dUv[g][k] = pk_load_buf(r_dU, row_off + (valid ? k * 16u : 0u), (T*)nullptr);
-          eid[g] = buf_i32(r_eid, valid && need_eid ? (uint32_t)(cs + g * G::CE + e_s) * 4u : kOOB);
-          const uint32_t rec_off = valid ? (uint32_t)ii[g] * (4u * rec_stride(H)) + h_s * 4u : kOOB;
-          r_el[g] = buf_f32(r_rec, rec_off);
-          r_lse[g] = buf_f32(r_rec, valid ? rec_off + 4u * H : kOOB);
-          Dsi[g] = buf_f32(r_rec, valid ? rec_off + 8u * H : kOOB);
-          if constexpr (rec_has_flag(H))
-            vflag[g] = __float_as_uint(buf_f32(r_rec, valid ? rec_off - h_s * 4u + 12u * H : kOOB));
-          else
-            vflag[g] = buf_u8(r_flag, valid ? (uint32_t)ii[g] : kOOB);
-        }
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-          const int32_t a = cs + (NG + g) * G::CE + e_s;
-          ii[g] = buf_i32(r_row, a < s1 ? (uint32_t)a * 4u : kOOB);
-        }
-        const float erh = er_tab;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-          const int32_t sl = cs + g * G::CE + e_s;
-          const bool valid = sl < s1;
-          const bool virt = vflag[g] != 0;
-          const float pre = r_el[g] + erh;
-          const float sv = virt ? 0.f : lrelu(pre, slope);
-          const float att = __expf(sv - r_lse[g]);
-          const float dropf = dropout_factor(dp, (uint64_t)eid[g] * H + h_s);
-          const float wv = valid ? att * dropf : 0.f;
-          float d[NV];
-#pragma unroll
-          for (int k = 0; k < NV; ++k) {
-            d[k] = pk_dot(dUv[g][k], hcv[k]);
-            acc[k] = pk_fma(wv, dUv[g][k], acc[k]);
-          }
-#pragma unroll
-          for (int o = 1; o < NV; o <<= 1)
-#pragma unroll
-            for (int k = 0; k < NV; k += 2 * o) d[k] = d[k] + d[k + o];
-          const float dsv = att * (d[0] * dropf - Dsi[g]);
-          const float dev = virt ? 0.f : dsv * (pre > 0.f ? 1.f : slope);
-          const uint32_t at = slot_de ? (uint32_t)sl : (uint32_t)eid[g];
-          buf_store_f32(r_de, valid ? at * (4u * H) + h_s * 4u : kOOB, dev);
-          xacc += valid ? dev : 0.f;
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const int32_t a = ns0 + g * G::CE + e_s;
-        ii[g] = buf_i32(r_row, a < ns1 ? (uint32_t)a * 4u : kOOB);
-      }
-#pragma unroll
-      for (int k = 0; k < NV; ++k)
-#pragma unroll
-        for (int o = H; o < 64; o <<= 1) acc[k] = pk_xor_add(acc[k], o);
+      st = cols_eh_column<H, F, T, false>(st, e_s, h_s, s0, s1, ns0, ns1, hcv, er_tab, nullptr,
+                                          r_row, r_eid, r_flag, r_rec, r_dU, r_de, need_eid,
+                                          slot_de, slope, dp);
       if (e_s == 0) {
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
-          pk_store(d_hc + (int64_t)jc * G::D + h_s * F + G::V * k, acc[k]);
-          pk_store(drow + h_s * F + G::V * k, acc[k]);
+          pk_store(d_hc + (int64_t)jc * G::D + h_s * F + G::V * k, st.acc[k]);
+          pk_store(drow + h_s * F + G::V * k, st.acc[k]);
         }
       }
-      xacc = wave_xor_sum<H>(xacc);
-      if (lane < H) d_er[(int64_t)jc * H + lane] = xacc;
-      fw_park(xrow, drow, avs, n2, e1, __shfl(xacc, hh), xv, hv2, cs1, cs2);
+      if (lane < H) d_er[(int64_t)jc * H + lane] = st.xacc;
+      fw_park(xrow, drow, avs, n2, e1, __shfl(st.xacc, hh), xv, hv2, cs1, cs2);
     }
     __syncthreads();
   }
